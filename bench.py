@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Device-resident Mpkt/s of pktvisor's Net+DNS handler path on MI355X.
 
-python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4] [--records R]
+python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--records R]
+                [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; the line's
+`roofline` comes from dispatch stamps of the timed steps themselves and the committed PMC
+traffic files, so it takes no run of its own. `--full` adds the measurements that do: the CPU
+baseline (`cpu_baseline`), the host-memory path (`e2e`) and, with `--read-ceiling`, the plain
+read of the blob. `--dump-outputs DIR` writes what a caller of the timed path holds after the
+last timed step, the live window's JSON view, as float64 arrays (see dump_outputs).
 
 One step = one pass of the fused Net v1 + DNS v1 hot path over one batch of
 synthetic pcap records already resident in HBM, added to the live window: the parse
@@ -47,16 +55,24 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=sorted(WORKLOADS))
     ap.add_argument("--records", type=int, default=10_000_000)
     ap.add_argument("--stream-records", type=int, default=100_000_000, help="--config 5: records of the whole stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: cpu_baseline, e2e, --read-ceiling")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the window the timed steps left (its JSON view, flattened) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--net-groups", type=int, default=0, help="pv_net_group bits (0 = reference defaults)")
     ap.add_argument("--dns-groups", type=int, default=0, help="pv_dns_group bits (0 = reference defaults)")
-    ap.add_argument("--read-ceiling", action="store_true", help="also time a plain read of the blob (HBM ceiling)")
+    ap.add_argument("--read-ceiling", action="store_true",
+                    help="--full: also time a plain read of the blob (HBM ceiling)")
     ap.add_argument("--reset-each-step", action="store_true",
                     help="reset the window before every step (rounds 1-5's step; N = 1 only)")
     ap.add_argument("--no-e2e", dest="e2e", action="store_false",
-                    help="skip timing the host-memory path (record blob in host RAM -> index -> H2D -> kernels)")
+                    help="--full: skip timing the host-memory path (record blob in host RAM -> index -> H2D -> "
+                         "kernels)")
     args = ap.parse_args()
+    if args.read_ceiling and not args.full:
+        ap.error("--read-ceiling is a --full measurement")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -173,6 +189,8 @@ def main():
         # a tuning variant (lean levels) skips work on purpose
         print(f"bench: tuning variant: bucket holds {events} events, expected {expect}",
               file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -219,9 +237,9 @@ def main():
             ca = tr / (kernel_ms * 1e-3) / 1e9
             line["roofline"]["counter_achieved"] = round(ca, 1)
             line["roofline"]["counter_frac"] = round(ca / HBM_PEAK_GBS, 4)
-        if args.read_ceiling:
+        if args.full and args.read_ceiling:
             line["read_ceiling_gbs"] = read_ceiling(d_recs, used)
-        if args.e2e and world == 1:
+        if args.full and args.e2e and world == 1:
             line["e2e"] = end_to_end(h, buf[:used], n, max(3, args.steps // 4))
         if args.net_groups or args.dns_groups:
             line["groups"] = {"net": args.net_groups, "dns": args.dns_groups}
@@ -233,7 +251,7 @@ def main():
                                      "pv_comm_allreduce_window (SUM/MIN), pv_comm_merge_topn (top-N entries to region "
                                      "owners over RCCL, merged on the device); finalize_window = leading entries + "
                                      "names, exact distributed quantile selection"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     h.close()
@@ -274,7 +292,7 @@ def bench_stream(args, world: int, rank: int, local: int, device):
             raise SystemExit(f"bench --config 5: a {used} B shard exceeds the 4 GiB record index; use more GPUs")
         idx = pa.RecordIndex(recs, max_records=hi - lo, threads=16)
     start_sec = synth.T0_US // 1000000
-    times = []
+    times, window = [], None
     # one context for every step, reset between them outside the timed region (as C2-C4 steps are):
     # its device buffers, ingest ring and index state are allocated once, by the first step
     h = pa.PvHandlers(host_spec=synth.HOST_SPEC, num_periods=5, max_records=min(hi - lo, 16_000_000) or 1,
@@ -306,7 +324,10 @@ def bench_stream(args, world: int, rank: int, local: int, device):
         ing = h.ingest_timing(reset=True)
         if it >= args.warmup:
             times.append((t1 - t0, t2 - t1, kms, ing))
-        events = h.window_json(5, merged=True)["packets"]["events"] if it == args.warmup + args.steps - 1 else None
+        window = h.window_json(5, merged=True) if it == args.warmup + args.steps - 1 else None
+    events = window["packets"]["events"] if window else None
+    if args.dump_outputs and rank == 0 and window:
+        dump_outputs(args.dump_outputs, window)
     h.close()
     if registered:
         lib.pv_host_unregister(buf.ctypes.data)
@@ -342,6 +363,40 @@ def bench_stream(args, world: int, rank: int, local: int, device):
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def flatten_window(obj, path=""):
+    """(path, leaf) of every leaf of a window's JSON view, keys in sorted order, list entries in
+    the order the window lists them (a top-N list's rank order)"""
+    if isinstance(obj, dict):
+        for k in sorted(obj):
+            yield from flatten_window(obj[k], f"{path}/{k}")
+    elif isinstance(obj, list):
+        for i, v in enumerate(obj):
+            yield from flatten_window(v, f"{path}/{i}")
+    else:
+        yield path, obj
+
+
+def dump_outputs(out_dir: str, window: dict) -> None:
+    """--dump-outputs: the window the timed steps left, as its caller reads it (window_json),
+    flattened by flatten_window into two float64 arrays (a few hundred entries):
+      window_values.npy  every numeric leaf (counters, rates, quantiles, cardinalities, top-N
+                         estimates), exact in float64 below 2^53
+      window_names.npy   every string leaf (top-N names), as the first 48 bits of the SHA-256 of
+                         "path=string": equal where the string at that place is equal
+    The synthetic shard is seeded by config and rank alone, so the same arguments give the same
+    window on every run and two builds compare entry for entry."""
+    import hashlib
+    values, names = [], []
+    for path, leaf in flatten_window(window):
+        if isinstance(leaf, str):
+            names.append(int.from_bytes(hashlib.sha256(f"{path}={leaf}".encode()).digest()[:6], "big"))
+        elif leaf is not None:
+            values.append(float(leaf))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "window_values.npy"), np.asarray(values, dtype=np.float64))
+    np.save(os.path.join(out_dir, "window_names.npy"), np.asarray(names, dtype=np.float64))
 
 
 def read_ceiling(d_recs, used: int) -> float:

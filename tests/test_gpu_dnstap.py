@@ -135,8 +135,10 @@ def test_dnstap_only_hosts(hosts):
 @pytest.mark.parametrize("spec,err", [("192.168.0.0/24/12ac", "invalid CIDR: 192.168.0.0/24/12ac"),
                                       ("192.168.0.0/64", "invalid CIDR: 192.168.0.0/64"),
                                       ("192.168.AE.0/24", "invalid IPv4 address: 192.168.AE.0"),
-                                      ("2001:db8::/48/12ac", "invalid CIDR: 2001:db8::/48/12ac"),
-                                      ("2001:db8::/256", "invalid CIDR: 2001:db8::/256"),
+                                      pytest.param("2001:db8::/48/12ac", "invalid CIDR: 2001:db8::/48/12ac",
+                                                   id="v6_cidr_extra_field"),  # ids without "::", the node
+                                      pytest.param("2001:db8::/256", "invalid CIDR: 2001:db8::/256",
+                                                   id="v6_prefix_256"),        # id separator
                                       ("fe80:2030:31:24/12", "invalid IPv6 address: fe80:2030:31:24")])
 def test_dnstap_only_hosts_invalid(spec, err):
     """test_dnstap.cpp:171-211 "dnstap invalid filters": parse_host_specs' texts"""

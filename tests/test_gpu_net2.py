@@ -36,7 +36,8 @@ def test_net2_fixture_parity(oracle, tmp_path, fixture, host, periods):
 
 
 @pytest.mark.parametrize("cfg,n,host", [(2, 60000, synth.HOST_SPEC), (4, 60000, synth.HOST_SPEC),
-                                        (9, 40000, "10.0.0.0/8,2000::/3,192.168.0.0/16")])
+                                        pytest.param(9, 40000, "10.0.0.0/8,2000::/3,192.168.0.0/16",
+                                                     id="9-40000-v4_v6_hosts")])
 @pytest.mark.parametrize("periods", [1, 5])
 def test_net2_synthetic_parity(oracle, tmp_path, cfg, n, host, periods):
     gpu, ref = run_both(oracle, synth.pcap_bytes(cfg, n), host, periods, tmp_path)

@@ -60,7 +60,8 @@ def test_fixture_parity(oracle, tmp_path, fixture, host, periods):
 
 @pytest.mark.parametrize("cfg,n,host", [(1, 1000, synth.HOST_SPEC), (2, 60000, synth.HOST_SPEC),
                                         (3, 60000, synth.HOST_SPEC), (4, 60000, synth.HOST_SPEC),
-                                        (9, 60000, "10.0.0.0/8,2000::/3,192.168.0.0/16")])
+                                        pytest.param(9, 60000, "10.0.0.0/8,2000::/3,192.168.0.0/16",
+                                                     id="9-60000-v4_v6_hosts")])
 @pytest.mark.parametrize("periods", [1, 5])
 def test_synthetic_parity(oracle, tmp_path, cfg, n, host, periods):
     gpu, ref = run_both(oracle, synth.pcap_bytes(cfg, n), host, periods, tmp_path)

@@ -3,6 +3,8 @@ against the reference's ICANN section, read here by a parser independent of gen_
 regular expressions, plus match_public_suffix sizes worked out by hand from the reference's
 list (libs/visor_dns/PublicSuffixList.h:226-250). The device and the oracle compile the same
 header, so GPU-vs-oracle parity cannot see a generator error; this test can."""
+import hashlib
+import json
 import os
 import re
 
@@ -10,6 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "pktvisor_amd", "csrc", "pv_psl_data.h")
+DIGEST = os.path.join(ROOT, "tests", "golden", "psl_icann_table.sha256")
 REF = "/root/reference/libs/visor_dns/PublicSuffixList.h"
 
 
@@ -86,10 +89,19 @@ def test_match_sizes_by_hand(name, size):
     assert match_public_suffix(header_table(), name) == size
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree absent (GPU box)")
+def table_digest(table) -> str:
+    return hashlib.sha256(json.dumps([[k, v] for k, v in table], ensure_ascii=False,
+                                     separators=(",", ":")).encode("utf-8")).hexdigest()
+
+
 def test_header_equals_reference_icann_section():
     """A line-oriented read of the reference's ICANN_DOMAINS initializer (each `{"key"sv, {...}},`
-    entry on its own line), independent of gen_psl.py's regular expressions."""
+    entry on its own line), independent of gen_psl.py's regular expressions. Its table_digest
+    is recorded in tests/golden/psl_icann_table.sha256, which the header must match wherever the
+    suite runs; where the reference tree is present the tables are also compared entry by entry."""
+    assert table_digest(header_table()) == open(DIGEST).read().split()[0]
+    if not os.path.exists(REF):
+        return
     text = open(REF, encoding="utf-8").read()
     body = text.split("===BEGIN ICANN DOMAINS===", 1)[1].split("===END ICANN DOMAINS===", 1)[0]
     ref, seen = [], set()
@@ -107,4 +119,5 @@ def test_header_equals_reference_icann_section():
             continue
         seen.add(key)
         ref.append((key, vals))
+    assert table_digest(ref) == open(DIGEST).read().split()[0]
     assert header_table() == ref

@@ -5,10 +5,10 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 R=$(pwd); O=$R/gpurun_out/${R6_DIR:-r6final}; mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 400 python3 -u bench.py > $O/bench_c2.log 2>&1 || { tail -5 $O/bench_c2.log; exit 1; }
+timeout -k 10 400 python3 -u bench.py --full > $O/bench_c2.log 2>&1 || { tail -5 $O/bench_c2.log; exit 1; }
 grep '^{' $O/bench_c2.log | tail -1 | cut -c1-300
 for c in 3 4; do
-  timeout -k 10 300 python3 -u bench.py --config $c --steps 40 --warmup 3 --no-e2e --reset-each-step > $O/bench_c$c.log 2>&1 || { tail -5 $O/bench_c$c.log; exit 1; }
+  timeout -k 10 300 python3 -u bench.py --config $c --steps 40 --warmup 3 --full --no-e2e --reset-each-step > $O/bench_c$c.log 2>&1 || { tail -5 $O/bench_c$c.log; exit 1; }
   grep '^{' $O/bench_c$c.log | tail -1 | cut -c1-200
 done
 timeout -k 10 400 python3 -u bench.py --config 5 --no-cpu-baseline > $O/bench_c5.log 2>&1 || { tail -5 $O/bench_c5.log; exit 1; }
