@@ -691,6 +691,8 @@ int pv_reset(pv_ctx *c)
     }
     c->started = c->ended = false;
     c->records_seen = 0;
+    c->seen_hi = 0; // (every slot is cleared before its next use: no entry keeps a seen flag)
+    c->seen_off = false;
     c->draws_net.reset(Jsf32());
     c->draws_dns.reset(Jsf32());
     c->dns_deep_now = true;
@@ -1897,6 +1899,11 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     P.tcp_emit = c->tcp_pre ? 0u : (c->tcp_exact_on() ? 7u : 1u);
     if (P.tcp_emit) launch_fill64(c, c->d_tmask, (n + 63) / 64, 0);
     P.gbase = c->global_base + c->records_seen;
+    // (a batch that starts below an index already processed, as after pv_set_global_base with a
+    // lower base, ends the trust in the seen flags until the next pv_reset)
+    if (P.gbase < c->seen_hi) c->seen_off = true;
+    c->seen_hi = std::max(c->seen_hi, P.gbase + n);
+    P.seen_trust = c->seen_off ? 0u : 1u;
     if (c->slow_defer && !c->edge_h) c->edge_h = (int64_t)first_sec + c->ttl_s + 61;
     if (c->sample_rate < 100) {
         // AbstractMetricsManager::new_event (:318-333): one draw per event of each manager, in
@@ -2254,7 +2261,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
                 for (int k = 0; k < 8; k++) ms[k] += (double)m[k];
             }
             fprintf(stderr, "pv_tstamps combine (%u wg): init=%.0f insert=%.0f count=%.0f scan=%.0f out=%.0f | merge (%lu wg): "
-                            "runs=%.0f load=%.0f insert=%.0f wb=%.0f names=%.0f\n",
+                            "runs=%.0f load=%.0f insert=%.0f names=%.0f wb=%.0f\n",
                     grid, cs[0] / grid, cs[1] / grid, cs[2] / grid, cs[3] / grid, cs[4] / grid, (unsigned long)nm,
                     ms[0] / std::max<uint64_t>(nm, 1), ms[1] / std::max<uint64_t>(nm, 1), ms[2] / std::max<uint64_t>(nm, 1),
                     ms[3] / std::max<uint64_t>(nm, 1), ms[4] / std::max<uint64_t>(nm, 1));

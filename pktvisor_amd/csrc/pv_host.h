@@ -693,6 +693,11 @@ struct pv_ctx {
     bool started = false, ended = false;
     int64_t last_sec = 0, last_nsec = 0;
     uint64_t global_base = 0, records_seen = 0;
+    // the top-N count words' seen flags (PV_CNT_SEEN_*) hold while record indices only grow:
+    // the highest gbase + n processed since the last pv_reset, and whether a batch started below
+    // it (then pv_topn_merge neither reads nor sets the flags until the next pv_reset)
+    uint64_t seen_hi = 0;
+    bool seen_off = false;
     // host copies of transaction values, per slot/kind
     std::vector<PvXValue> xvals_host;
     // merged top-N records from other ranks: table -> key -> (count, name)

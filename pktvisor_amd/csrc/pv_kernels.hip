@@ -470,7 +470,9 @@ __device__ __noinline__ void global_add(PV_CREF(PvParams) P, uint32_t slot, uint
         if (k == 0) {
             // slot clears reset keys only: an empty entry's count word holds what its last
             // occupant left, and nobody adds to it before its key is claimed, so the claimer
-            // reads it first (complete before the CAS issues) and adds its weight net of it
+            // reads it first (complete before the CAS issues) and adds its weight net of it (of
+            // the whole word: stale PV_CNT_SEEN_* flags go with it). The plain add of an existing
+            // entry leaves the entry's flags as they are: they stay true
             const uint64_t stale = __atomic_load_n(&P.tcnt[t.rbase + t.pos], __ATOMIC_RELAXED);
             asm volatile("" ::"v"((uint32_t)stale), "v"((uint32_t)(stale >> 32)) : "memory");
             uint64_t prev = atomicCAS((unsigned long long *)kp, 0ull, (unsigned long long)key);
@@ -3292,7 +3294,10 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
     if (threadIdx.x == 0) S.hm = 0;
     __syncthreads();
     TST(1)
-    // the table's entries per region (the spilled ones were counted as they spilled)
+    // the table's entries per region (the spilled ones were counted as they spilled). Counting
+    // an entry where its CAS claims it instead was measured and is slower: the claiming lanes are
+    // a fifth of a wave there (C2 insert phase 37.5K -> 56.3K cycles for this pass's 6.4K,
+    // profiles/r7/topn_seen)
     for (uint32_t j = threadIdx.x; j < CN; j += blockDim.x)
         if (S.key[j]) comb_count(P, S, comb_entry(S.key[j], S.cnt[j], S.rep[j]).x);
     __syncthreads();
@@ -3367,6 +3372,9 @@ extern "C" __global__ void __launch_bounds__(PV_CB_THREADS) pv_topn_combine_r12(
 #define PV_MG_THREADS 512
 #ifndef PV_MG_U2
 #define PV_MG_U2 4 // tuning: run entries in flight per merge thread
+#endif
+#ifndef PV_MG_SEEN
+#define PV_MG_SEEN 1 // the write-back skips IPv4 cardinality minima whose seen flag is set (0: submits all)
 #endif
 #define PV_MG_NN 640 // created named entries a workgroup lists in LDS (more go straight to the list)
 #define PV_CREATED (1ull << 63)
@@ -3481,6 +3489,7 @@ extern "C" __global__ void __launch_bounds__(PV_MG_THREADS) __attribute__((amdgp
     // direction 0's smallest index in the high half. Longer batches take a second pass.
     const bool narrow = P.n <= (1ull << 24) && !P.xmerge;
     const bool xm = P.xmerge != 0; // multi-GPU owner merge: 64-bit weights, no names, no CPC
+    const bool trust = PV_MG_SEEN && narrow && P.seen_trust; // the count words' seen flags are read and set
     uint32_t tabs = U.tabs << (hd * PV_SLOTS); // the tables among this run key's entries
     const bool one = !(tabs & (tabs - 1));
     bool fresh = true; // S.key still holds the DMA'd region
@@ -3586,7 +3595,12 @@ extern "C" __global__ void __launch_bounds__(PV_MG_THREADS) __attribute__((amdgp
         TST(3)
         // write-back of the entries this batch changed: a created entry's key and weight; an
         // existing one's count word read (all of a thread's reads in flight together) and stored
-        // with the weight added. Then the IPv4 cardinality minima of the changed v1 entries.
+        // with the weight added. Then the IPv4 cardinality minima of the changed v1 entries, for
+        // the directions whose seen flag (PV_CNT_SEEN_*, pv_layout.h) is still clear: a flagged
+        // direction's coupon is in the CPC table with a smaller record index than this batch can
+        // carry, so neither the coupon nor the atomicMin is needed. The directions submitted here
+        // get their flag with the count's store. Without trust the flags are not read (every
+        // minimum is submitted) and ride through cc + dd unchanged.
         constexpr uint32_t WB = PF < 4 ? PF : 4;
         for (uint32_t q0 = 0; q0 < PF; q0 += WB) {
             uint64_t kk[WB], dd[WB], cc[WB];
@@ -3609,15 +3623,20 @@ extern "C" __global__ void __launch_bounds__(PV_MG_THREADS) __attribute__((amdgp
                     st_nt<PV_NT_MERGE, uint64_t>(P.tkeys + rbase + i, mv4_norm(kk[q]) & ~PV_MV4);
                     if (xm && PV_KEY_METRIC(kk[q] & ~PV_CREATED) != TM_IPV4) P.taux[rbase + i] = 0; // name unknown here
                 }
-                if (dd[q]) st_nt<PV_NT_MERGE, uint64_t>(P.tcnt + rbase + i, cc[q] + dd[q]);
+                uint64_t nf = 0; // the flags this write-back sets
                 if ((kk[q] & PV_MV4) && dd[q]) {
                     const uint32_t m0 = (uint32_t)(S.dl[i] >> 32), m1 = (uint32_t)(kk[q] >> 32) & 0xffffffu;
-                    if (m0 != 0xffffffffu || m1 != 0xffffffu) {
+                    const uint64_t seen = trust ? cc[q] : 0; // (a created entry's cc is 0: no flags)
+                    const bool s0 = m0 != 0xffffffffu && !(seen & PV_CNT_SEEN_SRC);
+                    const bool s1 = m1 != 0xffffffu && !(seen & PV_CNT_SEEN_DST);
+                    if (s0 || s1) {
                         const uint32_t cp = ip4_coupon((uint32_t)kk[q]);
-                        if (m0 != 0xffffffffu) cpc_min(P, s, CPC_SRC, cp, (int64_t)(P.gbase + m0));
-                        if (m1 != 0xffffffu) cpc_min(P, s, CPC_DST, cp, (int64_t)(P.gbase + m1));
+                        if (s0) cpc_min(P, s, CPC_SRC, cp, (int64_t)(P.gbase + m0));
+                        if (s1) cpc_min(P, s, CPC_DST, cp, (int64_t)(P.gbase + m1));
+                        if (trust) nf = (s0 ? PV_CNT_SEEN_SRC : 0ull) | (s1 ? PV_CNT_SEEN_DST : 0ull);
                     }
                 }
+                if (dd[q]) st_nt<PV_NT_MERGE, uint64_t>(P.tcnt + rbase + i, (cc[q] + dd[q]) | nf);
             }
         }
         if (threadIdx.x == 0 && S.ncr) atomicAdd(&P.tab_live[tb], S.ncr);
@@ -3733,7 +3752,7 @@ extern "C" __global__ void __launch_bounds__(256) pv_topn_xwrite(const PvParams 
     uint32_t at = off[PV_XC(tb / PV_SLOTS, r, tb % PV_SLOTS, P.reg_log2)] + block_excl_scan(c, wsum, tot);
     for (uint32_t i = i0; i < i0 + per; i++) {
         const uint64_t k = P.tkeys[rb + i];
-        if (k) out[at++] = make_ulonglong2(k | ((uint64_t)(tb % PV_SLOTS) << 60), P.tcnt[rb + i]);
+        if (k) out[at++] = make_ulonglong2(k | ((uint64_t)(tb % PV_SLOTS) << 60), P.tcnt[rb + i] & PV_CNT_MASK);
     }
 }
 
@@ -3859,7 +3878,7 @@ extern "C" __global__ void __launch_bounds__(1024) pv_topn_purge(const PvParams 
     for (uint32_t q = 0; q < PER; q++) {
         const uint32_t i = threadIdx.x + q * blockDim.x;
         k[q] = i < rs ? P.tkeys[rbase + i] : 0;
-        c[q] = i < rs ? P.tcnt[rbase + i] : 0;
+        c[q] = i < rs ? P.tcnt[rbase + i] & PV_CNT_MASK : 0; // (survivors are stored without their seen flags)
         a[q] = i < rs ? P.taux[rbase + i] : 0;
         if (k[q]) {
             atomicAdd(&live, 1u);

@@ -158,6 +158,15 @@ enum {
 #define PV_MAX_GRID 1024   // Net/DNS-pass workgroups per batch (pv_topn_merge's run table)
 #define PV_MAX_REGIONS_LOG2 12 // table_log2 <= PV_REGION_LOG2 + PV_MAX_REGIONS_LOG2
 #define PV_PROBES 256
+// Count word of a top-N entry: the count in bits 0..61 and, for a v1 IPv4 entry, two "seen"
+// flags. A flag says that the slot's CPC table of that direction already holds this address's
+// coupon with a record index no later batch can go below (indices grow from batch to batch), so
+// pv_topn_merge's write-back skips the coupon and its atomicMin. Only that write-back sets a
+// flag, and only while PvParams::seen_trust holds; flags 0 is always safe (it costs the old
+// work), so any writer may drop them, and every reader of a count masks them off.
+#define PV_CNT_SEEN_SRC (1ull << 62) // CPC_SRC has the address's coupon
+#define PV_CNT_SEEN_DST (1ull << 63) // CPC_DST has it
+#define PV_CNT_MASK ((1ull << 62) - 1)
 // entry of the new-name list (pv_topn_merge -> pv_topn_names)
 struct PvNewName {
     uint32_t slot; // table (PV_TSLOT)
@@ -454,6 +463,8 @@ struct PvParams {
     uint32_t cb_grid;     // combine workgroups: ceil(grid_main / cb_fan)
     uint32_t xmerge;      // pv_topn_merge over received multi-GPU entries (64-bit weights, no names)
     uint32_t x_lo, x_hi;  // its regions [x_lo, x_hi)
+    uint32_t seen_trust;  // record indices have only grown since the last reset: pv_topn_merge may read and
+                          // set the count words' PV_CNT_SEEN_* flags (0: it does neither)
     uint32_t dbg; // profiling knob (PV_DEBUG_STAGES env): 1 stop after staging, 2 after parse, 4 no DNS lane,
                   // 16 no DNS name decode, 32 no DNS table updates
     PV_G uint32_t *flags;

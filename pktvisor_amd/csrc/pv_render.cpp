@@ -48,7 +48,7 @@ int read_topn(pv_ctx *c, uint32_t s, std::vector<TopRec> &out) // s: table (PV_T
         // a purged region's survivors report count + the thetas its purges subtracted (the
         // frequent-items estimate, exact for a key no purge dropped)
         const uint64_t off = roff.empty() ? 0 : roff[(i >> (c->tcap_log2 - c->reg_log2))];
-        TopRec r{keys[i], cnt[i] + off, std::string()};
+        TopRec r{keys[i], (cnt[i] & PV_CNT_MASK) + off, std::string()}; // (the count word without its seen flags)
         uint32_t m = PV_KEY_METRIC(keys[i]);
         if (m == TM_IPV4) {
             uint32_t ip = (uint32_t)keys[i];

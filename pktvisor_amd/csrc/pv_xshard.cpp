@@ -519,7 +519,7 @@ int pv_topn_x_candidates(pv_ctx *c, uint8_t **blob, size_t *bytes)
             const std::vector<uint64_t> &roff = c->roff[tb];
             for (size_t i = 0; i < n; i++)
                 if (x->keys[i])
-                    ents.push_back(XE{x->keys[i], x->cnt[i] + (roff.empty() ? 0 : roff[lo + (i >> rsl)]), tb, x->aux[i], s});
+                    ents.push_back(XE{x->keys[i], (x->cnt[i] & PV_CNT_MASK) + (roff.empty() ? 0 : roff[lo + (i >> rsl)]), tb, x->aux[i], s});
         }
         std::sort(ents.begin(), ents.end(), [](const XE &p1, const XE &p2) { return p1.key < p2.key; });
         const size_t NZ = sets.size();
