@@ -610,6 +610,80 @@ int pv_set_kernel_timing(pv_ctx *ctx, uint32_t every);
 const char *pv_net_kernel_name(pv_ctx *ctx);
 int pv_kernel_timing(pv_ctx *ctx, double *total_ms, uint64_t *launches, int reset);
 
+/* ---- GeoIP / ASN databases (MaxMind DB 2.0), the reference's MaxmindDB (src/GeoDB.h:27-41,
+ * src/GeoDB.cpp). A database is parsed from untrusted bytes and compiled at open time: every data
+ * record the search tree reaches is rendered once to the string the Net handler counts by, City
+ * as _getGeoLoc (GeoDB.cpp:179-244: continent code, "/" country name (iso_code when names.en is
+ * absent), "/" first subdivision iso_code, "/" city name; latitude and longitude as "%f"), ASN as
+ * _getASNString (:371-413: the number, then "/" organization when present). Equal strings share
+ * one dense dictionary id, ordered by the first data offset that renders them, so every process
+ * that opens the same file gets the same ids; id 0 is "Unknown", a lookup without an entry. The
+ * search tree becomes two uint32 words a node, every child index validated. The reader needs no
+ * GPU and no context; its messages are pv_geodb_last_error (this thread). PV_EINVAL: a file that
+ * is not a well-formed database (record_size other than 24 / 28 / 32, ip_version other than 4 / 6,
+ * a node_count or data pointer outside the file, a pointer to a pointer, nesting beyond 32). */
+typedef struct pv_geodb pv_geodb;
+enum pv_geodb_kind { PV_GEODB_CITY = 0, PV_GEODB_ASN = 1 };
+int pv_geodb_open(const uint8_t *bytes, size_t len, uint32_t kind, pv_geodb **db);
+int pv_geodb_open_file(const char *path, uint32_t kind, pv_geodb **db);
+void pv_geodb_close(pv_geodb *db);
+const char *pv_geodb_last_error(void);
+/* dictionary size (ids 0 .. entries-1) and one entry; the strings live as long as the database.
+ * ASN entries have empty lat / lon. */
+uint32_t pv_geodb_entries(const pv_geodb *db);
+/* a hash of the compiled tree and dictionary: equal on every rank of a sharded run that attached
+ * the same file (the ranks' dense counts are summed id by id, pktvisor_amd.dist checks it) */
+uint64_t pv_geodb_hash(const pv_geodb *db);
+int pv_geodb_entry(const pv_geodb *db, uint32_t id, const char **name, const char **lat, const char **lon);
+/* dictionary ids of n addresses of addr_len 4 or 16 bytes each (network order), walked through the
+ * compiled tree on the host. An IPv4 address in an ip_version 6 tree starts at the node 96 zero bits
+ * reach, as libmaxminddb does; an IPv6 address in an ip_version 4 tree has no entry. */
+int pv_geodb_lookup(const pv_geodb *db, const uint8_t *addrs, size_t n, uint32_t addr_len, uint32_t *ids);
+/* Attach the databases to a context (either may be NULL; call before the first batch): the
+ * reference's HandlerModulePlugin::city / asn (--geo-city / --geo-asn). The compiled trees and
+ * dictionaries are copied; the databases may be closed afterwards. With the Net v1 top_geo
+ * group enabled, top_geoLoc / top_ASN then count the address top_ipv4 / top_ipv6 count of every
+ * deep packet of known direction (NetworkMetricsBucket::_process_geo_metrics,
+ * net/v1/NetStreamHandler.cpp:745-794), each database independently: exact counts per dictionary
+ * id and bucket, walked once per distinct address of a batch part (pv_geo_count over the top-N
+ * combine lists), summed by window merges, external buckets (by string) and the multi-GPU
+ * reduce (pv_window_regions lists them). JSON, Prometheus and OpenTelemetry carry them
+ * (geo_loc with lat / lon when both exist, asn). Not built, and refused with PV_EUNSUPPORTED
+ * while a database is attached: Net v2, DNS v2, the DNS top_ecs group, the DNS geoloc_notfound /
+ * asn_notfound filters and pv_process_dnstap. With top_ips disabled the passes still log the IP
+ * entries the counts come from; the outputs then show no top_ipv4 / top_ipv6. The Net geo filters are not built either: they stay net_filter_all. */
+int pv_set_geodb(pv_ctx *ctx, const pv_geodb *city, const pv_geodb *asn);
+/* The Net v1 handler's geo filters, the typed form of the "geoloc_notfound", "asn_notfound",
+ * "only_geoloc_prefix" and "only_asn_number" config keys (NetStreamHandler::start,
+ * net/v1/NetStreamHandler.cpp:61-88; applied as _filtering :223-283). A filtered packet is an
+ * event plus `filtered` and nothing else. The geoloc family (geoloc_notfound adds the prefix
+ * "Unknown") passes a packet when a prefix is a prefix of its remote address's location; the ASN
+ * family (asn_notfound adds "Unknown", only_asn_number entries are digits stored as number + "/")
+ * the same on the ASN string; both families must pass. A family that is set filters every packet
+ * of unknown direction, and every packet while its database is not attached. The verdict is
+ * computed on the device (pv_geo_verdict: one walk per record and family, one pass bit per
+ * dictionary id) and read by the general Net pass. Call before the first batch, before or after
+ * pv_set_geodb; NULL clears. PV_EINVAL with the reference's text for a non-digit ASN number;
+ * PV_EUNSUPPORTED with deep_sample_rate below 100. pv_config.net_filter_all stays what it was. */
+typedef struct pv_net_filters {
+    uint32_t geoloc_notfound;        /* nonzero: "geoloc_notfound": true */
+    uint32_t asn_notfound;           /* nonzero: "asn_notfound": true */
+    uint32_t only_geoloc_prefix_set; /* nonzero: the key exists (an empty list then passes nothing) */
+    uint32_t n_geoloc_prefixes;
+    const char *const *geoloc_prefixes;
+    uint32_t only_asn_number_set;
+    uint32_t n_asn_numbers;
+    const char *const *asn_numbers;  /* digit strings */
+} pv_net_filters;
+int pv_set_net_filters(pv_ctx *ctx, const pv_net_filters *f);
+/* pv_geodb_hash of the attached city and ASN databases (0: none): what the ranks of a sharded run
+ * compare before they sum their windows. pv_comm_allreduce_window compares them itself; a caller
+ * that moves the pv_window_regions words with its own transport compares these first. */
+int pv_geodb_hashes(pv_ctx *ctx, uint64_t hashes[2]);
+/* pv_geodb_lookup on the device (pv_geo_walk, one lane an address, at most 32 or 128 dependent
+ * loads) through the attached database of `kind`; addrs and ids are host memory. */
+int pv_geodb_lookup_device(pv_ctx *ctx, uint32_t kind, const uint8_t *addrs, size_t n, uint32_t addr_len, uint32_t *ids);
+
 #ifdef __cplusplus
 }
 #endif

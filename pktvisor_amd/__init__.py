@@ -61,6 +61,13 @@ class pv_dns_filters(ctypes.Structure):
                 ("xact_dirs_disabled", ctypes.c_uint32)]
 
 
+class pv_net_filters(ctypes.Structure):
+    _fields_ = [("geoloc_notfound", ctypes.c_uint32), ("asn_notfound", ctypes.c_uint32),
+                ("only_geoloc_prefix_set", ctypes.c_uint32), ("n_geoloc_prefixes", ctypes.c_uint32),
+                ("geoloc_prefixes", ctypes.POINTER(ctypes.c_char_p)), ("only_asn_number_set", ctypes.c_uint32),
+                ("n_asn_numbers", ctypes.c_uint32), ("asn_numbers", ctypes.POINTER(ctypes.c_char_p))]
+
+
 from pktvisor_amd.config import ConfigException as ConfigError  # noqa: E402  (the reference's texts)
 from pktvisor_amd.config import StreamHandlerException  # noqa: E402,F401
 
@@ -175,7 +182,10 @@ EXPORTS = ["pv_version", "pv_device_count", "pv_create", "pv_destroy", "pv_last_
            "pv_afpacket_stats", "pv_afpacket_close", "pv_afpacket_last_error", "pv_set_bpf", "pv_bpf_validate",
            "pv_bpf_run", "pv_bpf_filter_records", "pv_comm_merge_topn", "pv_topn_x_export", "pv_topn_x_import",
            "pv_topn_x_candidates", "pv_topn_x_names", "pv_topn_x_view", "pv_values_x_select", "pv_comm_values_select",
-           "pv_slow_x_finish", "pv_comm_slow_finish"]
+           "pv_slow_x_finish", "pv_comm_slow_finish", "pv_geodb_open", "pv_geodb_open_file", "pv_geodb_close",
+           "pv_geodb_last_error", "pv_geodb_entries", "pv_geodb_hash", "pv_geodb_hashes", "pv_set_net_filters", "pv_geodb_entry", "pv_geodb_lookup", "pv_set_geodb",
+           "pv_geodb_lookup_device"]
+PV_GEODB_CITY, PV_GEODB_ASN = 0, 1
 # pv_allreduce_fn: (uint64_t *buf, size_t n, int op, void *user) -> int
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
 PV_HANDLER_NET, PV_HANDLER_DNS = 1, 2
@@ -346,6 +356,22 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.pv_afpacket_close.argtypes = [P]
     lib.pv_afpacket_close.restype = None
     lib.pv_afpacket_last_error.restype = ctypes.c_char_p
+    lib.pv_geodb_open.argtypes = [P, ctypes.c_size_t, U32, ctypes.POINTER(P)]
+    lib.pv_geodb_open_file.argtypes = [ctypes.c_char_p, U32, ctypes.POINTER(P)]
+    lib.pv_geodb_close.argtypes = [P]
+    lib.pv_geodb_close.restype = None
+    lib.pv_geodb_last_error.restype = ctypes.c_char_p
+    lib.pv_geodb_entries.argtypes = [P]
+    lib.pv_geodb_entries.restype = U32
+    lib.pv_set_net_filters.argtypes = [P, ctypes.POINTER(pv_net_filters)]
+    lib.pv_geodb_hashes.argtypes = [P, ctypes.POINTER(ctypes.c_uint64)]
+    lib.pv_geodb_hash.argtypes = [P]
+    lib.pv_geodb_hash.restype = U64
+    lib.pv_geodb_entry.argtypes = [P, U32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p),
+                                   ctypes.POINTER(ctypes.c_char_p)]
+    lib.pv_geodb_lookup.argtypes = [P, P, ctypes.c_size_t, U32, P]
+    lib.pv_set_geodb.argtypes = [P, P, P]
+    lib.pv_geodb_lookup_device.argtypes = [P, U32, P, ctypes.c_size_t, U32, P]
     _lib = lib
     return lib
 
@@ -438,6 +464,73 @@ def dnstap_reader(path: str, periods: int = 1, only_hosts: Optional[list] = None
 def pcap_file_bytes(records: bytes, linktype: int = 1, ts_nano: int = 0) -> bytes:
     magic = 0xA1B23C4D if ts_nano else 0xA1B2C3D4
     return struct.pack("<IHHiIII", magic, 2, 4, 0, 0, 262144, linktype) + records
+
+
+def _packed_addrs(addrs, addr_len: int) -> np.ndarray:
+    """addresses (bytes of addr_len each, or one bytes / uint8 array of them back to back) as one array"""
+    if isinstance(addrs, np.ndarray):
+        buf = np.ascontiguousarray(addrs, dtype=np.uint8).reshape(-1)
+    elif isinstance(addrs, (bytes, bytearray)):
+        buf = np.frombuffer(bytes(addrs), dtype=np.uint8)
+    else:
+        buf = np.frombuffer(b"".join(addrs), dtype=np.uint8)
+    if addr_len not in (4, 16) or buf.size % addr_len:
+        raise PvError(f"addresses must be {addr_len} bytes each (4 or 16)")
+    return buf
+
+
+class GeoDB:
+    """A MaxMind DB file (GeoIP2 City or ISP / ASN) read and compiled on the host (pv_geodb_open):
+    the reference's MaxmindDB (src/GeoDB.h:27-41). kind: "city" or "asn". Needs no GPU.
+    `entries` is the dictionary of rendered strings, (name, lat, lon) per id; id 0 is "Unknown"."""
+
+    def __init__(self, source, kind: str = "city"):
+        if kind not in ("city", "asn"):
+            raise PvError(f"GeoDB kind must be 'city' or 'asn', not {kind!r}")
+        self.lib = load_library()
+        self.kind = PV_GEODB_CITY if kind == "city" else PV_GEODB_ASN
+        self.ptr = ctypes.c_void_p()
+        if isinstance(source, (bytes, bytearray)):
+            data = bytes(source)
+            rc = self.lib.pv_geodb_open(data, len(data), self.kind, ctypes.byref(self.ptr))
+        else:
+            rc = self.lib.pv_geodb_open_file(os.fsencode(source), self.kind, ctypes.byref(self.ptr))
+        if rc:
+            self.ptr = None
+            raise PvError(f"pv_geodb_open failed ({rc}): {self.lib.pv_geodb_last_error().decode()}")
+        self.hash = int(self.lib.pv_geodb_hash(self.ptr))  # of the compiled tree and dictionary
+        self.entries = []
+        n, l, o = ctypes.c_char_p(), ctypes.c_char_p(), ctypes.c_char_p()
+        for i in range(self.lib.pv_geodb_entries(self.ptr)):
+            self.lib.pv_geodb_entry(self.ptr, i, ctypes.byref(n), ctypes.byref(l), ctypes.byref(o))
+            self.entries.append((n.value.decode("utf-8", "replace"), l.value.decode(), o.value.decode()))
+
+    def lookup_ids(self, addrs, addr_len: int) -> np.ndarray:
+        """dictionary ids of packed addresses (network order), walked on the host"""
+        buf = _packed_addrs(addrs, addr_len)
+        ids = np.empty(buf.size // addr_len, dtype=np.uint32)
+        rc = self.lib.pv_geodb_lookup(self.ptr, buf.ctypes.data, ids.size, addr_len, ids.ctypes.data)
+        if rc:
+            raise PvError(f"pv_geodb_lookup failed ({rc}): {self.lib.pv_geodb_last_error().decode()}")
+        return ids
+
+    def lookup(self, address: str):
+        """(name, lat, lon) of one textual address"""
+        import socket
+        fam = socket.AF_INET6 if ":" in address else socket.AF_INET
+        raw = socket.inet_pton(fam, address)
+        return self.entries[int(self.lookup_ids(raw, len(raw))[0])]
+
+    def close(self):
+        if self.ptr:
+            self.lib.pv_geodb_close(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Bucket:
@@ -599,11 +692,12 @@ class PvHandlers:
                  dns_config: Optional[dict] = None, topn_percentile_threshold: int = 0,
                  net2_config: Optional[dict] = None, dns2_config: Optional[dict] = None,
                  deep_sample_rate: int = 100, tcp_packet_reassembly_cache_limit: int = 0, bpf=None,
-                 tcp_exact_lru: bool = False):
+                 tcp_exact_lru: bool = False, geo_city_db=None, geo_asn_db=None):
         from pktvisor_amd import config as pvcfg
         self.lib = load_library()
         filt = dns_filter_config(dns_filters) if dns_filters else None
         net_filter_all = 0
+        net_filters = None
         self.dnstap_mask = 0
         net2_groups = 0
         if net2_config is not None:
@@ -627,7 +721,12 @@ class PvHandlers:
             num_periods = win.get("num_periods", num_periods)
             topn_count = win.get("topn_count", topn_count)
             topn_percentile_threshold = win.get("topn_percentile_threshold", topn_percentile_threshold)
-            n, d = pvcfg.net_start(ncfg), pvcfg.dns_start(dcfg)
+            # (with a database attached the geo filters are typed and matched on the device)
+            geo_on = (geo_city_db is not None, geo_asn_db is not None)
+            n, d = pvcfg.net_start(ncfg, geo_enabled=geo_on if any(geo_on) else None), pvcfg.dns_start(dcfg)
+            net_filters = n.get("filters")
+            if net_filters:
+                n["filter_all"] = False  # pv_set_net_filters decides, family by family
             net_groups, dns_groups, net_filter_all = n["groups"], d["groups"], int(n["filter_all"])
             if dns2_config is None:
                 filt = d["filters"]
@@ -679,6 +778,56 @@ class PvHandlers:
             self._check(self.lib.pv_set_tcp_exact_lru(self.ctx, 1), "pv_set_tcp_exact_lru")
         if bpf:
             self.set_bpf(bpf)
+        if geo_city_db is not None or geo_asn_db is not None:
+            self.set_geodb(geo_city_db, geo_asn_db)
+        if net_filters:
+            self.set_net_filters(**net_filters)
+
+    def set_net_filters(self, geoloc_notfound=False, asn_notfound=False, only_geoloc_prefix=None, only_asn_number=None):
+        """the Net handler's geo filters on the attached databases (pv_set_net_filters); a list of
+        None means the key is absent. Before the first batch."""
+        f = pv_net_filters(int(bool(geoloc_notfound)), int(bool(asn_notfound)))
+        keep = []
+        for name, lst in (("geoloc_prefixes", only_geoloc_prefix), ("asn_numbers", only_asn_number)):
+            if lst is None:
+                continue
+            arr = (ctypes.c_char_p * max(1, len(lst)))(*[str(x).encode() for x in lst])
+            keep.append(arr)
+            setattr(f, name, ctypes.cast(arr, ctypes.POINTER(ctypes.c_char_p)))
+            setattr(f, "n_" + name, len(lst))
+            setattr(f, "only_geoloc_prefix_set" if name == "geoloc_prefixes" else "only_asn_number_set", 1)
+        self._check(self.lib.pv_set_net_filters(self.ctx, ctypes.byref(f)), "pv_set_net_filters")
+
+    def set_geodb(self, city=None, asn=None):
+        """attach GeoIP databases (a path or a GeoDB each; pv_set_geodb), the reference's --geo-city /
+        --geo-asn: the Net handler's top_geo group then fills top_geoLoc / top_ASN, and
+        geo_lookup_device walks them. Before the first batch."""
+        own = []
+        dbs = []
+        for src, kind in ((city, "city"), (asn, "asn")):
+            if src is not None and not isinstance(src, GeoDB):
+                src = GeoDB(src, kind)
+                own.append(src)
+            dbs.append(src)
+        try:
+            self._check(self.lib.pv_set_geodb(self.ctx, dbs[0].ptr if dbs[0] else None, dbs[1].ptr if dbs[1] else None),
+                        "pv_set_geodb")
+            # (pktvisor_amd.dist.check_aligned: every rank of a sharded run must hold the same)
+            hs = (ctypes.c_uint64 * 2)()
+            self._check(self.lib.pv_geodb_hashes(self.ctx, hs), "pv_geodb_hashes")
+            self.geo_hashes = [int(hs[0]), int(hs[1])]
+        finally:
+            for d in own:  # the context keeps its own copy of the trees
+                d.close()
+
+    def geo_lookup_device(self, kind: str, addrs, addr_len: int) -> np.ndarray:
+        """GeoDB.lookup_ids through the device walker and the attached database of `kind`"""
+        buf = _packed_addrs(addrs, addr_len)
+        ids = np.empty(buf.size // addr_len, dtype=np.uint32)
+        self._check(self.lib.pv_geodb_lookup_device(self.ctx, PV_GEODB_CITY if kind == "city" else PV_GEODB_ASN,
+                                                    buf.ctypes.data, ids.size, addr_len, ids.ctypes.data),
+                    "pv_geodb_lookup_device")
+        return ids
 
     def set_bpf(self, insns):
         """the pcap input's "bpf" filter as its compiled classic-BPF program (pv_set_bpf): records it

@@ -129,24 +129,40 @@ def window_config(cfgs) -> dict:
     return out
 
 
-def net_start(cfg: dict) -> dict:
+def net_start(cfg: dict, geo_enabled=None) -> dict:
     """NetStreamHandler::start (src/handlers/net/v1/NetStreamHandler.cpp:45-130) up to the
-    signal wiring: {"groups": bits | GROUPS_SET, "filter_all": bool}"""
+    signal wiring: {"groups": bits | GROUPS_SET, "filter_all": bool}.
+
+    geo_enabled = (city database enabled, ASN database enabled), the reference's
+    HandlerModulePlugin::city / asn: the geo filters then come back typed under "filters"
+    (the pv_net_filters fields), and "filter_all" is set only where a configured filter family has
+    no database (_filtering :223-283: !enabled() => will_filter). Without the keyword no database
+    is enabled and the result is what it always was."""
     validate_configs(cfg, NET_CONFIG_DEFS)
     groups = process_groups(cfg, NET_GROUP_DEFS, NET_DEFAULT_GROUPS)
     out = {"groups": groups | GROUPS_SET, "filter_all": False}
+    filters = {"geoloc_notfound": False, "asn_notfound": False, "only_geoloc_prefix": None, "only_asn_number": None}
     # the geo / ASN filters match a MaxMind lookup; with no database enabled every packet is
     # filtered (_filtering :223-283: !city->enabled() => will_filter)
-    if _bool(cfg, "geoloc_notfound") or _bool(cfg, "asn_notfound"):
-        out["filter_all"] = True
+    city_on, asn_on = (bool(geo_enabled[0]), bool(geo_enabled[1])) if geo_enabled is not None else (False, False)
+    if _bool(cfg, "geoloc_notfound"):
+        filters["geoloc_notfound"] = True
+    if _bool(cfg, "asn_notfound"):
+        filters["asn_notfound"] = True
     if "only_geoloc_prefix" in cfg:
-        _string_list(cfg, "only_geoloc_prefix")
-        out["filter_all"] = True
+        filters["only_geoloc_prefix"] = list(_string_list(cfg, "only_geoloc_prefix"))
     if "only_asn_number" in cfg:
-        for number in _string_list(cfg, "only_asn_number"):
+        numbers = list(_string_list(cfg, "only_asn_number"))
+        for number in numbers:
             if not number.isdigit():
                 raise ConfigException(f"NetStreamHandler: only_asn_number filter contained an invalid/unsupported value: {number}")
+        filters["only_asn_number"] = numbers
+    geoloc = filters["geoloc_notfound"] or filters["only_geoloc_prefix"] is not None
+    asn = filters["asn_notfound"] or filters["only_asn_number"] is not None
+    if (geoloc and not city_on) or (asn and not asn_on):
         out["filter_all"] = True
+    if geo_enabled is not None and (geoloc or asn):
+        out["filters"] = filters
     return out
 
 

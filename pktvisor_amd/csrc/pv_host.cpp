@@ -121,6 +121,8 @@ void clear_part(pv_ctx *c, int part, uint32_t s)
     if (part == PART_NET) {
         launch_fill64(c, sum, PV_SUM_NET_WORDS, 0);
         launch_fill64(c, cpc, PV_MIN_NET_WORDS, (uint64_t)PV_CPC_EMPTY);
+        for (auto &g : c->geo)
+            if (g.d_cnt) launch_fill64(c, (uint64_t *)g.d_cnt + (uint64_t)s * g.dict.size(), g.dict.size(), 0);
     } else {
         launch_fill64(c, sum + PV_OFF_DNS, PV_SUM_WORDS - PV_OFF_DNS, 0);
         launch_fill64(c, cpc + PV_MIN_NET_WORDS, PV_MIN_WORDS - PV_MIN_NET_WORDS, (uint64_t)PV_CPC_EMPTY);
@@ -306,6 +308,162 @@ int pv_set_tcp_exact_lru(pv_ctx *c, int on)
     return 0;
 }
 
+static int nf_build(pv_ctx *c);
+int pv_set_geodb(pv_ctx *c, const pv_geodb *city, const pv_geodb *asn)
+{
+    if (!c) return PV_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->records_seen) return c->fail(PV_EINVAL, "the geo databases must be set before the first batch");
+    const pv_geodb *dbs[2] = {city, asn};
+    for (uint32_t k = 0; k < 2; k++)
+        if (dbs[k] && dbs[k]->kind != k)
+            return c->fail(PV_EINVAL, "pv_set_geodb: the %s database was opened as the other kind", k ? "ASN" : "city");
+    if (city || asn) {
+        // what a database would have to feed and does not yet: refused, not approximated
+        if (c->net2_groups) return c->fail(PV_EUNSUPPORTED, "geo databases: the Net v2 handler's top_geo is not built");
+        if (c->dns2_groups) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS v2 handler's geo metrics are not built");
+        if (c->dns_groups & PV_DNS_TOP_ECS) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS top_ecs group's geo metrics are not built");
+        if (c->f_flags & PVDF_FILTER_ALL) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS geoloc_notfound / asn_notfound filters are not built");
+    }
+    hipError_t e = hipSetDevice(c->device);
+    if (!hip_ok(e)) return c->hipfail(e, "geo database");
+    // both databases are built aside and swapped in together: a failure leaves the context as it was
+    pv_ctx::GeoAttach next[2];
+    auto drop = [](pv_ctx::GeoAttach &g) {
+        if (g.d_tree) hipFree(g.d_tree);
+        if (g.d_cnt) hipFree(g.d_cnt);
+        g = pv_ctx::GeoAttach();
+    };
+    for (uint32_t k = 0; k < 2; k++) {
+        if (!dbs[k]) continue;
+        pv_ctx::GeoAttach &g = next[k];
+        const size_t bytes = dbs[k]->tree.size() * 4, cbytes = (size_t)PV_SLOTS * dbs[k]->dict.size() * 8;
+        // (an empty tree still gets a word, so the kernel's pointer is never null)
+        if (!hip_ok(e = hipMalloc(&g.d_tree, std::max<size_t>(bytes, 8))) ||
+            (bytes && !hip_ok(e = hipMemcpy(g.d_tree, dbs[k]->tree.data(), bytes, hipMemcpyHostToDevice))) ||
+            !hip_ok(e = hipMalloc(&g.d_cnt, cbytes)) || !hip_ok(e = hipMemset(g.d_cnt, 0, cbytes))) {
+            drop(next[0]);
+            drop(next[1]);
+            return c->hipfail(e, "geo database tree and counts");
+        }
+        g.dict = dbs[k]->dict;
+        g.node_count = dbs[k]->node_count;
+        g.start4 = dbs[k]->start4;
+        g.ip_version = dbs[k]->ip_version;
+        g.hash = dbs[k]->hash;
+        g.on = true;
+    }
+    hipStreamSynchronize(c->stream); // (nothing in flight reads the old trees: no batch has run)
+    for (uint32_t k = 0; k < 2; k++) {
+        drop(c->geo[k]);
+        c->geo[k] = std::move(next[k]);
+    }
+    return nf_build(c); // (filters set earlier match the new dictionaries)
+}
+
+// The pass tables of the geo filters: per family one byte per dictionary id, 1 where a configured
+// prefix is a prefix of the id's string (begins_with, net/v1/NetStreamHandler.cpp:218-221).
+// Called with c->mu held, whenever the databases or the filters change.
+static int nf_build(pv_ctx *c)
+{
+    hipError_t e = hipSetDevice(c->device);
+    for (int k = 0; k < 2; k++) {
+        if (c->d_nf_pass[k]) hipFree(c->d_nf_pass[k]);
+        c->d_nf_pass[k] = nullptr;
+    }
+    if (!c->nf_verdicts()) return 0;
+    for (int k = 0; k < 2; k++) {
+        if (!c->nf_on[k]) continue;
+        const auto &dict = c->geo[k].dict;
+        std::vector<uint8_t> pass(dict.size(), 0);
+        for (size_t i = 0; i < dict.size(); i++)
+            for (const std::string &pre : c->nf_prefix[k])
+                if (dict[i].name.size() >= pre.size() && !dict[i].name.compare(0, pre.size(), pre)) { pass[i] = 1; break; }
+        if (!hip_ok(e = hipMalloc(&c->d_nf_pass[k], pass.size())) ||
+            !hip_ok(e = hipMemcpy(c->d_nf_pass[k], pass.data(), pass.size(), hipMemcpyHostToDevice)))
+            return c->hipfail(e, "geo filter pass table");
+    }
+    if (!c->d_gfilt) {
+        // (one bit a record, padded so a wave past the span's end writes and reads in bounds)
+        const size_t words = (size_t)(c->max_records / 64 + 8);
+        if (!hip_ok(e = hipMalloc(&c->d_gfilt, words * 8)) || !hip_ok(e = hipMemset(c->d_gfilt, 0, words * 8)))
+            return c->hipfail(e, "geo filter verdicts");
+    }
+    return 0;
+}
+
+int pv_set_net_filters(pv_ctx *c, const pv_net_filters *f)
+{
+    if (!c) return PV_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->records_seen) return c->fail(PV_EINVAL, "Net filters must be set before the first batch");
+    bool on[2] = {false, false};
+    std::vector<std::string> pre[2];
+    if (f) {
+        // NetStreamHandler::start's filter setup (net/v1/NetStreamHandler.cpp:61-88)
+        if (f->geoloc_notfound) { on[0] = true; pre[0].push_back("Unknown"); }
+        if (f->asn_notfound) { on[1] = true; pre[1].push_back("Unknown"); }
+        if (f->only_geoloc_prefix_set) {
+            on[0] = true;
+            for (uint32_t i = 0; i < f->n_geoloc_prefixes; i++) pre[0].push_back(f->geoloc_prefixes[i] ? f->geoloc_prefixes[i] : "");
+        }
+        if (f->only_asn_number_set) {
+            on[1] = true;
+            for (uint32_t i = 0; i < f->n_asn_numbers; i++) {
+                const std::string n = f->asn_numbers[i] ? f->asn_numbers[i] : "";
+                if (!std::all_of(n.begin(), n.end(), [](unsigned char ch) { return std::isdigit(ch); }))
+                    return c->fail(PV_EINVAL, "NetStreamHandler: only_asn_number filter contained an invalid/unsupported value: %s", n.c_str());
+                pre[1].push_back(n + "/");
+            }
+        }
+    }
+    if ((on[0] || on[1]) && c->sample_rate < 100)
+        return c->fail(PV_EUNSUPPORTED, "deep_sample_rate below 100 with geo filters is not built");
+    for (int k = 0; k < 2; k++) { c->nf_on[k] = on[k]; c->nf_prefix[k] = pre[k]; }
+    return nf_build(c);
+}
+
+int pv_geodb_hashes(pv_ctx *c, uint64_t hashes[2])
+{
+    if (!c || !hashes) return PV_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    for (int k = 0; k < 2; k++) hashes[k] = c->geo[k].on ? c->geo[k].hash : 0;
+    return 0;
+}
+
+int pv_geodb_lookup_device(pv_ctx *c, uint32_t kind, const uint8_t *addrs, size_t n, uint32_t addr_len, uint32_t *ids)
+{
+    if (!c) return PV_EINVAL;
+    if (kind > PV_GEODB_ASN || (addr_len != 4 && addr_len != 16) || (n && (!addrs || !ids)))
+        return c->fail(PV_EINVAL, "pv_geodb_lookup_device: bad argument");
+    const pv_ctx::GeoAttach &g = c->geo[kind];
+    if (!g.on) return c->fail(PV_EINVAL, "pv_geodb_lookup_device: no %s database attached (pv_set_geodb)", kind ? "ASN" : "city");
+    if (!n) return 0;
+    if (addr_len == 16 && g.ip_version != 6) { // an IPv6 address in an IPv4 tree: no entry
+        std::fill(ids, ids + n, 0u);
+        return 0;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipError_t e = hipSetDevice(c->device);
+    uint32_t *d_addrs = nullptr, *d_ids = nullptr;
+    int rc = 0;
+    if (!hip_ok(e) || !hip_ok(e = hipMalloc(&d_addrs, n * addr_len)) || !hip_ok(e = hipMalloc(&d_ids, n * 4)) ||
+        !hip_ok(e = hipMemcpy(d_addrs, addrs, n * addr_len, hipMemcpyHostToDevice))) {
+        rc = c->hipfail(e, "geo lookup buffers");
+    } else {
+        const uint32_t start = addr_len == 4 ? g.start4 : (g.node_count ? 0u : PV_GEO_LEAF);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 2048);
+        hipLaunchKernelGGL(pv_geo_walk, dim3(grid), dim3(256), 0, c->stream, (const uint32_t *)g.d_tree, g.node_count, start,
+                           (const uint32_t *)d_addrs, (uint64_t)n, addr_len / 4, d_ids);
+        if (!hip_ok(e = hipGetLastError()) || !hip_ok(e = hipStreamSynchronize(c->stream)) ||
+            !hip_ok(e = hipMemcpy(ids, d_ids, n * 4, hipMemcpyDeviceToHost)))
+            rc = c->hipfail(e, "pv_geo_walk");
+    }
+    if (d_addrs) hipFree(d_addrs);
+    if (d_ids) hipFree(d_ids);
+    return rc;
+}
+
 // the public_suffix_list table on the device and the per-record suffix sizes (v1 and v2)
 static int psl_setup(pv_ctx *c)
 {
@@ -402,6 +560,8 @@ int pv_set_dns_filters(pv_ctx *c, const pv_dns_filters *f)
     if (f->only_queries) fl |= PVDF_ONLY_QUERIES;
     if (f->only_responses) fl |= PVDF_ONLY_RESPONSES;
     if (f->only_dnssec_response) fl |= PVDF_ONLY_DNSSEC;
+    if (f->filter_all && (c->geo[0].on || c->geo[1].on))
+        return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS geoloc_notfound / asn_notfound filters are not built");
     if (f->filter_all) fl |= PVDF_FILTER_ALL;
     if (f->n_qtypes > PV_MAX_QTYPES) return c->fail(PV_EINVAL, "only_qtype: at most %d qtypes", PV_MAX_QTYPES);
     for (uint32_t k = 0; k < f->n_qtypes; k++)
@@ -635,6 +795,11 @@ void pv_destroy(pv_ctx *c)
                     c->d_xcnt, c->d_xrhdr, c->d_xtot, c->d_xsend, c->d_xrecv, c->d_xp, c->d_bpf, c->d_fwork, c->d_frecs,
                     c->d_foffs, c->d_fsc, c->d_fscan, c->d_eoc, c->d_eoc_cnt};
     for (void *p : ptrs) if (p) hipFree(p);
+    for (void *p : {(void *)c->d_nf_pass[0], (void *)c->d_nf_pass[1], (void *)c->d_gfilt}) if (p) hipFree(p);
+    for (auto &g : c->geo) {
+        if (g.d_tree) hipFree(g.d_tree);
+        if (g.d_cnt) hipFree(g.d_cnt);
+    }
     if (c->d_dbits) hipFree(c->d_dbits);
     for (void *hp : {(void *)c->h_params, (void *)c->h_xparams, (void *)c->h_status, (void *)c->h_dbits, (void *)c->h_tcpcnt,
                      (void *)c->h_tparams})
@@ -898,11 +1063,12 @@ void params_common(pv_ctx *c, PvParams &P, const uint8_t *d_recs, const uint32_t
     P.n = n;
     P.linktype = c->cfg.linktype;
     P.ts_nano = c->cfg.ts_nano;
-    P.net_groups = c->net_groups;
+    P.net_groups = c->dev_net_groups();
     P.dns_groups = c->dns_groups;
     P.net2_groups = c->net2_groups;
     P.dns2_groups = c->dns2_groups;
-    P.net_filter_all = c->cfg.net_filter_all ? 1u : 0u;
+    P.net_filter_all = (c->cfg.net_filter_all || c->nf_all()) ? 1u : 0u;
+    P.gfilt = c->nf_verdicts() ? (const uint64_t *)c->d_gfilt : nullptr;
     P.nets = c->nets;
     P.f_flags = c->f_flags;
     P.f_rcode_mask = c->f_rcode_mask;
@@ -2106,7 +2272,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     // forces one for A/B runs.
     static const char *force = getenv("PV_NET_KERNEL");
     // (every TCP packet for the exact LRU replay: the general pass emits them)
-    const bool general = P.n_shift || P.net_filter_all || P.dbg || P.ndeep_net || c->tcp_exact_on() ||
+    const bool general = P.n_shift || P.net_filter_all || P.gfilt || P.dbg || P.ndeep_net || c->tcp_exact_on() ||
                          (force && !strcmp(force, "general"));
     const uint32_t reg_grid = std::min<uint32_t>(grid, (uint32_t)(c->cus * c->reg_wg_per_cu));
     const uint64_t per_wave = ((uint64_t)P.wt_per_block / 4 + 1) * ((grid + reg_grid - 1) / reg_grid); // packed lane counters
@@ -2117,7 +2283,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     P.ip_compact = lean ? 1u : 0u;
     P.ip_base = ((uint64_t)P.slot_of[0] << 60) | ((uint64_t)TM_IPV4 << 56) |
                 ((uint64_t)((c->net_groups & PV_NET_CARDINALITY) ? 1 : 0) << 33);
-    const bool tc = (c->net_groups & PV_NET_TOP_IPS) != 0;
+    const bool tc = (c->dev_net_groups() & PV_NET_TOP_IPS) != 0;
     // PV_NET_KERNEL=span: the span-load pass (top-IPs groups), kept for A/B runs
     const bool span = lean && tc && force && !strcmp(force, "span");
     // both lean passes defer general-path records to pv_net_slow_list
@@ -2158,6 +2324,22 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     // asks for are stamped)
     const bool timed = c->timing_every && (c->timing_ctr++ % c->timing_every) == 0;
     hipEvent_t e0 = timed ? c->ev_start : nullptr, e1 = timed ? c->ev_stop : nullptr;
+    if (P.gfilt) {
+        // the geo filters' verdict of every record of the span, for the general pass to read
+        PvGeoArgs G{};
+        for (int k = 0; k < 2; k++) {
+            const pv_ctx::GeoAttach &g = c->geo[k];
+            if (!g.on) continue;
+            G.tree[k] = g.d_tree;
+            G.node_count[k] = g.node_count;
+            G.start4[k] = g.start4;
+            G.ip_version[k] = g.ip_version;
+            G.entries[k] = (uint32_t)g.dict.size();
+        }
+        hipLaunchKernelGGL(pv_geo_verdict, dim3((uint32_t)((P.n + 255) / 256)), dim3(256), 0, st, dp, G,
+                           (const uint8_t *)(c->nf_on[0] ? c->d_nf_pass[0] : nullptr),
+                           (const uint8_t *)(c->nf_on[1] ? c->d_nf_pass[1] : nullptr), c->d_gfilt);
+    }
     if (general) hipExtLaunchKernelGGL(pv_net_kernel, dim3(grid), dim3(PV_NET_THREADS), 0, st, e0, e1, 0, dp);
     else if (lean) {
         // the lean pass, then its deferred general-path records (the dispatch stamps span both)
@@ -2192,6 +2374,22 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     }
     hipLaunchKernelGGL(c->reg_log2 <= 10 ? pv_topn_combine : pv_topn_combine_r12, dim3(P.cb_grid), dim3(cb_threads), 0, st,
                        (const PvParams *)c->d_params);
+    if (c->geo_counting()) {
+        // top_geo: one walk per combined IP entry (pv_geo_count reads the combine lists; the merge does not change them)
+        PvGeoArgs G{};
+        for (int k = 0; k < 2; k++) {
+            const pv_ctx::GeoAttach &g = c->geo[k];
+            if (!g.on) continue;
+            G.tree[k] = g.d_tree;
+            G.cnt[k] = g.d_cnt;
+            G.node_count[k] = g.node_count;
+            G.start4[k] = g.start4;
+            G.ip_version[k] = g.ip_version;
+            G.entries[k] = (uint32_t)g.dict.size();
+        }
+        hipLaunchKernelGGL(pv_geo_count, dim3(std::min<uint32_t>(P.cb_grid, (uint32_t)c->cus * 8)), dim3(256), 0, st,
+                           (const PvParams *)c->d_params, G);
+    }
     hipLaunchKernelGGL(pv_topn_merge, dim3(2u << c->reg_log2), dim3(pv_topn_merge_threads()), 0, st, (const PvParams *)c->d_params);
     // names: as many workgroups as are resident (LDS: two per CU), each pipelining its entries
     hipLaunchKernelGGL((P.f_flags & (PVDF_ONLY_QSUFFIX | PVDF_PSL)) ? pv_topn_names_sfx : pv_topn_names, dim3((uint32_t)c->cus * 2),
@@ -2884,6 +3082,7 @@ int pv_process_dnstap(pv_ctx *c, const uint8_t *buf, size_t bytes, uint32_t msg_
 {
     std::lock_guard<std::mutex> g(c->mu);
     if (int rc = merged_refuse(c)) return rc;
+    if (c->geo[0].on || c->geo[1].on) return c->fail(PV_EUNSUPPORTED, "geo databases: the dnstap input's geo metrics are not built");
     hipSetDevice(c->device);
     std::vector<pvi::DtMessage> msgs;
     uint32_t frames = 0;

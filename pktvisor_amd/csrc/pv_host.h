@@ -40,6 +40,7 @@
 
 #include "../../include/pvgpu.h"
 #include "pv_ingest.h"
+#include "pv_geodb.h"
 #include "pv_layout.h"
 
 // The kernel's name fingerprint (pv_parse.h NameStats + fp56), compiled for the host so
@@ -155,6 +156,12 @@ extern "C" __global__ void pv_topn_merge(const PvParams *P);
 extern "C" __global__ void pv_topn_names_sfx(const PvParams *P);
 extern "C" __global__ void pv_topn_name_fix(const PvParams *P, uint32_t tb);
 extern "C" uint32_t pv_topn_merge_threads();
+// pv_geo.hip: the walk of a compiled GeoIP / ASN tree, one lane an address
+extern "C" __global__ void pv_geo_walk(const uint32_t *tree, uint32_t node_count, uint32_t start, const uint32_t *addrs, uint64_t n,
+                                       uint32_t addr_words, uint32_t *ids);
+extern "C" __global__ void pv_geo_count(const PvParams *P, PvGeoArgs G);
+extern "C" __global__ void pv_geo_verdict(const PvParams *P, PvGeoArgs G, const uint8_t *pass_city, const uint8_t *pass_asn,
+                                          unsigned long long *out);
 struct PvBpfIns;
 extern "C" __global__ void pv_bpf_keep(const uint8_t *recs, const uint32_t *offs, uint32_t n, const PvBpfIns *prog, uint32_t ninsn,
                                        uint32_t *sz, uint32_t *kf);
@@ -485,12 +492,34 @@ struct Json {
         if (after_key) { after_key = false; return; }
         if (n.back()++) s += ',';
     }
-    void esc(const std::string &v)
+    // true if v is well-formed UTF-8 (shortest forms, no surrogates, up to U+10FFFF)
+    static bool is_utf8(const std::string &v)
     {
+        for (size_t i = 0; i < v.size();) {
+            const unsigned char c = (unsigned char)v[i];
+            const int n = c < 0x80 ? 0 : (c >> 5) == 6 ? 1 : (c >> 4) == 14 ? 2 : (c >> 3) == 30 ? 3 : -1;
+            if (n < 0 || v.size() - i <= (size_t)n) return false; // (cut short)
+            uint32_t cp = n == 0 ? c : c & (0x3f >> n);
+            for (int k = 1; k <= n; k++) {
+                const unsigned char d = (unsigned char)v[i + k];
+                if ((d & 0xc0) != 0x80) return false;
+                cp = (cp << 6) | (d & 0x3f);
+            }
+            static const uint32_t lo[4] = {0, 0x80, 0x800, 0x10000};
+            if (cp < lo[n] || cp > 0x10ffff || (cp >= 0xd800 && cp < 0xe000)) return false;
+            i += n + 1;
+        }
+        return true;
+    }
+    // text = true: a UTF-8 string (GeoIP names) goes out as it is when it is well formed
+    void esc(const std::string &v, bool text = false)
+    {
+        const bool raw = text && is_utf8(v);
         s += '"';
         for (unsigned char c : v) {
             if (c == '"') s += "\\\"";
             else if (c == '\\') s += "\\\\";
+            else if (raw && c >= 0x80) s += (char)c;
             else if (c < 0x20 || c >= 0x80) { char b[8]; snprintf(b, sizeof b, "\\u%04x", c); s += b; } // bytes >= 0x80 as U+0080..U+00FF
             else s += (char)c;
         }
@@ -498,6 +527,7 @@ struct Json {
     }
     Json &key(const std::string &k) { sep(); esc(k); s += ':'; after_key = true; return *this; }
     void str(const std::string &v) { sep(); esc(v); }
+    void text(const std::string &v) { sep(); esc(v, true); }
     void u(uint64_t v) { sep(); s += std::to_string(v); }
     void i(int64_t v) { sep(); s += std::to_string(v); }
     void d(double v)
@@ -528,6 +558,34 @@ struct XQuant {
 };
 
 struct pv_ctx {
+    // the attached GeoIP databases (pv_set_geodb), [PV_GEODB_CITY] and [PV_GEODB_ASN]: the compiled
+    // tree on the device and what a walk needs of its header
+    struct GeoAttach {
+        uint32_t *d_tree = nullptr;
+        uint32_t node_count = 0, start4 = PV_GEO_LEAF, ip_version = 0;
+        uint64_t hash = 0;
+        bool on = false;
+        // per Net slot, one exact u64 packet count per dictionary id (PV_SLOTS x dict.size());
+        // cleared with the slot's Net part, summed by window folds and the multi-GPU reduce
+        unsigned long long *d_cnt = nullptr;
+        std::vector<pv_geodb::Entry> dict;
+    } geo[2];
+    // Net geo filters (pv_set_net_filters): per family ([0] geoloc, [1] ASN) whether it is on, its
+    // prefix list ("Unknown" for *_notfound, "<number>/" for only_asn_number), one pass byte per
+    // dictionary id on the device (built at the first batch), and the per-record verdict bitmap
+    bool nf_on[2] = {false, false};
+    std::vector<std::string> nf_prefix[2];
+    uint8_t *d_nf_pass[2] = {nullptr, nullptr};
+    bool nf_ready = false;
+    unsigned long long *d_gfilt = nullptr;
+    // a family that is on without its database filters every packet (_filtering: !enabled())
+    bool nf_all() const { return (nf_on[0] && !geo[0].on) || (nf_on[1] && !geo[1].on); }
+    bool nf_verdicts() const { return (nf_on[0] || nf_on[1]) && !nf_all() && !cfg.net_filter_all; }
+    bool geo_counting() const { return (geo[0].on || geo[1].on) && (net_groups & PV_NET_TOP_GEO); }
+    // The Net groups as the device passes see them. top_geo counts from the IP entries of the
+    // top-N pipeline, so while it counts, the passes log and combine those entries even with
+    // top_ips disabled; the outputs follow net_groups and then show no top_ipv4 / top_ipv6.
+    uint32_t dev_net_groups() const { return net_groups | (geo_counting() ? (uint32_t)PV_NET_TOP_IPS : 0u); }
     std::vector<pv_bpf_insn> bpf; // the pcap input's BPF program (pv_set_bpf), empty = none
     // the program on the device and the filtered batch (pv_process_device runs the filter there)
     pv_bpf_insn *d_bpf = nullptr;

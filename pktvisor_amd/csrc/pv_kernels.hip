@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "pv_layout.h"
+#include "pv_geodb.h"
 
 #define PV_BLOCK 256
 #define PV_C __attribute__((address_space(4)))
@@ -1225,6 +1226,7 @@ struct NetK {
     PV_G uint32_t *tseg_cnt;
     PV_G uint64_t *tmask;
     const PV_G uint32_t *ndeep_net, *ndeep_dns; // deep sampling (general pass only)
+    const PV_G uint64_t *gfilt;                 // geo filter verdicts (general pass only)
 };
 // Net v1 counters of one record straight to HBM (a lane whose slot is not the wave's
 // register slot: records of a 64-record tile that holds a period shift)
@@ -1265,7 +1267,7 @@ __device__ void knet_flush(const NetK &K, uint32_t s, NetCtr &c)
     PV_KFLUSH1(s, PV_OFF_NET + NC_V4, c.n4, nc) PV_KFLUSH1(s, PV_OFF_NET + NC_V6, c.n6, nc)
     PV_KFLUSH1(s, PV_OFF_NET + NC_UDP, c.nudp, nc) PV_KFLUSH1(s, PV_OFF_NET + NC_TCP, c.ntcp, nc)
     PV_KFLUSH1(s, PV_OFF_NET + NC_SYN, c.nsyn, nc) PV_KFLUSH1(s, PV_OFF_NET + NC_OTHER, c.noth, nc)
-    if (K.net_filter_all) PV_KFLUSH1(s, PV_OFF_NET + NC_FILTERED, c.nfilt, nc)
+    if (K.net_filter_all || K.gfilt) PV_KFLUSH1(s, PV_OFF_NET + NC_FILTERED, c.nfilt, nc)
     c.zero();
 }
 
@@ -1724,6 +1726,7 @@ __device__ __forceinline__ void net_pass(const PvParams *__restrict__ Pp)
     K.n_dshift = P.n_dshift; K.dskip_before = P.dskip_before;
     K.tcp_emit = P.tcp_emit; K.tseg_cap = P.tseg_cap; K.tseg = P.tseg; K.tseg_cnt = P.tseg_cnt; K.tmask = P.tmask;
     K.ndeep_net = GEN ? P.ndeep_net : nullptr; K.ndeep_dns = GEN ? P.ndeep_dns : nullptr;
+    K.gfilt = GEN ? P.gfilt : nullptr;
     const ParseCfg C = parse_cfg(P);
     const uint64_t n = K.n, last = n - 1;
     const uint64_t nwt = (n + PV_WT - 1) / PV_WT;
@@ -1826,6 +1829,8 @@ __device__ __forceinline__ void net_pass(const PvParams *__restrict__ Pp)
             deep = !((K.ndeep_net[i >> 5] >> (i & 31)) & 1);
             ddeep = !((K.ndeep_dns[i >> 5] >> (i & 31)) & 1);
         }
+        // this record's geo filter verdict (_filtering with a database, :223-283), or every record's
+        const bool gf = K.net_filter_all || (GEN && K.gfilt && active && ((K.gfilt[i >> 6] >> (i & 63)) & 1));
         const uint32_t base = b0 & ~15u, nch = (b1 - base + 15) >> 4;
         const bool packed = nch <= (uint32_t)(PV_NL_SLOT / 16);
         uint32_t hv = PV_NOH;
@@ -1860,7 +1865,7 @@ __device__ __forceinline__ void net_pass(const PvParams *__restrict__ Pp)
             if (!fast) {
                 // a record that is not deep: no IPs, no SYN (NetworkMetricsBucket::process_packet
                 // !deep, net/v1/NetStreamHandler.cpp:518-521)
-                const SlowOut so = net_slow(R, C, P, K, off, i, slot, upd && !K.net_filter_all && deep);
+                const SlowOut so = net_slow(R, C, P, K, off, i, slot, upd && !gf && deep);
                 o.caplen = so.caplen; o.dir = so.dir; o.l3 = so.l3; o.l4 = so.l4; o.syn = so.syn && deep;
                 ek = so.ek;
                 dm = so.dm;
@@ -1888,7 +1893,7 @@ __device__ __forceinline__ void net_pass(const PvParams *__restrict__ Pp)
             STAMP(4)
             if (K.dbg & 2) {
                 c.add(o);
-            } else if (K.net_filter_all) {
+            } else if (gf) {
                 // process_filtered (net/v1/NetStreamHandler.cpp:507-514): an event and `filtered` only
                 if (upd) {
                     if (own) { c.nev++; c.nfilt++; }
@@ -2080,7 +2085,7 @@ __device__ __forceinline__ SlowOut net_slow_p(const PvParams *__restrict__ Pp, c
     K.net_groups = P.net_groups; K.dbg = 0; K.net_filter_all = 0;
     K.n_dshift = P.n_dshift; K.dskip_before = P.dskip_before;
     K.tcp_emit = P.tcp_emit; K.tseg_cap = P.tseg_cap; K.tseg = P.tseg; K.tseg_cnt = P.tseg_cnt; K.tmask = P.tmask;
-    K.ndeep_net = nullptr; K.ndeep_dns = nullptr;
+    K.ndeep_net = nullptr; K.ndeep_dns = nullptr; K.gfilt = nullptr;
     return net_slow_body(R, parse_cfg(P), P, K, off, i, K.slot0, true);
 }
 
@@ -2328,7 +2333,7 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
         c.noth += (uint32_t)((cl >> 32) & 0xffff); c.nsyn += (uint32_t)(cl >> 48);
     }
     NetK K;
-    K.sum = P.sum; K.net_groups = groups; K.net_filter_all = 0;
+    K.sum = P.sum; K.net_groups = groups; K.net_filter_all = 0; K.gfilt = nullptr;
     if (any) knet_flush(K, slot, c);
     lds_barrier();
     for (uint32_t b = threadIdx.x; b < PV_HBINS; b += blockDim.x)
@@ -2555,7 +2560,7 @@ extern "C" __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_pe
         c.noth += (uint32_t)((cl >> 32) & 0xffff); c.nsyn += (uint32_t)(cl >> 48);
     }
     NetK K;
-    K.sum = P.sum; K.net_groups = groups; K.net_filter_all = 0;
+    K.sum = P.sum; K.net_groups = groups; K.net_filter_all = 0; K.gfilt = nullptr;
     knet_flush(K, slot, c);
     lds_barrier();
     for (uint32_t b = threadIdx.x; b < PV_HBINS; b += blockDim.x)
@@ -2611,7 +2616,7 @@ extern "C" __global__ void __launch_bounds__(256) pv_net_slow_list(const PvParam
         if (P.tcp_emit && so.l4 == 6) atomicOr(reinterpret_cast<unsigned long long *>(P.tmask + t), 1ull << (i & 63));
     }
     NetK K;
-    K.sum = P.sum; K.net_groups = P.net_groups; K.net_filter_all = 0;
+    K.sum = P.sum; K.net_groups = P.net_groups; K.net_filter_all = 0; K.gfilt = nullptr;
     knet_flush(K, slot, c);
 }
 
@@ -5317,4 +5322,125 @@ extern "C" __global__ void __launch_bounds__(256) pv_bpf_secs_compact(const uint
 extern "C" hipError_t pv_exclusive_scan_u32(void *tmp, size_t *tmp_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s)
 {
     return rocprim::exclusive_scan(tmp, *tmp_bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s);
+}
+
+// GeoIP / ASN counting (NetworkMetricsBucket::_process_geo_metrics, net/v1/NetStreamHandler.cpp:
+// 376-385,433-442: the address top_ipv4 / top_ipv6 count, looked up in each enabled database).
+// Runs behind pv_topn_combine over its lists: one entry per distinct address (and direction) of
+// a combine workgroup's records, with the number of packets as its weight, so a heavy hitter
+// costs one tree walk per list instead of one per packet. An IPv4 entry carries the address in
+// its key; an IPv6 key is a hash, so the address is read from the entry's record (the smallest
+// record index among its packets), as the IPv6 name writer reads it. One lane an entry; the
+// walk is pv_geo_step32's (bounded by the address bits, never past node_count); the weight goes
+// to the slot's dense count of the dictionary id.
+extern "C" __global__ void __launch_bounds__(256) pv_geo_count(const PvParams *__restrict__ Pp, PvGeoArgs G)
+{
+    PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
+    const uint64_t keymask = (1ull << 60) - 1;
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint32_t blk = blockIdx.x; blk < P.cb_grid; blk += gridDim.x) {
+        const PV_G ulonglong2 *list = reinterpret_cast<const PV_G ulonglong2 *>(P.cb) + (uint64_t)blk * P.cb_fan * P.mq_cap;
+        const uint32_t cnt = min(P.cb_cnt[blk], P.cb_fan * P.mq_cap);
+        // (whole waves stay in the loop: the counting below votes across the wave)
+        for (uint32_t j0 = 0; j0 < cnt; j0 += blockDim.x) {
+            const uint32_t j = j0 + threadIdx.x;
+            uint32_t words = 0, a[4] = {0, 0, 0, 0}, w = 0, slot = 0;
+            if (j < cnt) {
+                const ulonglong2 e = list[j];
+                const uint64_t key = e.x & keymask;
+                const uint32_t metric = PV_KEY_METRIC(key);
+                slot = (uint32_t)(e.x >> 60);
+                if (metric == TM_IPV4 && !PV_IS_V2_IP4(key)) {
+                    a[0] = __builtin_bswap32((uint32_t)key); // the key holds the address as the record's bytes load
+                    words = 1;
+                    w = (uint32_t)e.y & PV_W_CNT;
+                } else if (metric == TM_IPV6 && !PV_IS_V2_IP6(key)) {
+                    const uint32_t rep = (uint32_t)(e.y >> 32);
+                    if (rep < P.n) {
+                        Parsed o;
+                        const GAcc R{P.recs};
+                        parse_record(R, P, P.offs[rep], o);
+                        if (o.has6) {
+                            const uint64_t at = ip6_name_addr(R, o, key);
+                            for (int k = 0; k < 4; k++) a[k] = __builtin_bswap32(R.u32(at + 4 * k));
+                            words = 4;
+                            w = (uint32_t)e.y;
+                        }
+                    }
+                }
+            }
+            for (int k = 0; k < 2; k++) {
+                if (!G.tree[k]) continue; // (uniform)
+                uint32_t id = 0;
+                if (words == 1 || (words == 4 && G.ip_version[k] == 6)) {
+                    uint32_t t = words == 1 ? G.start4[k] : (G.node_count[k] ? 0u : PV_GEO_LEAF);
+                    for (uint32_t q = 0; q < words; q++) t = pv_geo_step32(G.tree[k], G.node_count[k], t, a[q]);
+                    id = pv_geo_id(t);
+                }
+                if (id >= G.entries[k]) id = 0; // (a compiled tree holds no such id)
+                // Most addresses of real traffic share a few ids ("Unknown", the big networks), and
+                // one atomic per entry on the same word serialises (8.5 ms a C2 batch, measured).
+                // The wave's lanes of one (slot, id) add their weights first: up to four such groups
+                // a step, led by the lowest lane left; what remains goes one atomic a lane.
+                const uint64_t word = words ? (uint64_t)slot * G.entries[k] + id : ~0ull;
+                uint64_t todo = __ballot(words != 0);
+                for (int r = 0; r < 4 && todo; r++) {
+                    const int lead = __ffsll((unsigned long long)todo) - 1;
+                    const uint64_t lw = __shfl(word, lead, 64);
+                    const bool mine = words && word == lw;
+                    const uint64_t m = __ballot(mine);
+                    unsigned long long sum = mine ? w : 0ull;
+                    if (m & (m - 1)) // more than one lane
+                        for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o, 64);
+                    if ((int)lane == lead) atomicAdd(&G.cnt[k][lw], sum);
+                    todo &= ~m;
+                }
+                if (words && ((todo >> lane) & 1)) atomicAdd(&G.cnt[k][word], (unsigned long long)w);
+            }
+        }
+    }
+}
+
+// The Net geo filters' verdict per record (NetStreamHandler::_filtering, net/v1/NetStreamHandler.cpp:
+// 223-283), ahead of the general Net pass, which consumes it next to its net_filter_all branch.
+// One lane a record: direction and remote address from the parse, one walk per filter family
+// whose pass table is given, and the family's pass bit of the dictionary id (the host matched the
+// prefix lists against the dictionary, so no string work here). Unknown direction is filtered;
+// a packet that is neither IPv4 nor IPv6 passes, as in the reference. One u64 a wave.
+extern "C" __global__ void __launch_bounds__(256)
+pv_geo_verdict(const PvParams *__restrict__ Pp, PvGeoArgs G, const uint8_t *__restrict__ pass_city,
+               const uint8_t *__restrict__ pass_asn, unsigned long long *__restrict__ out)
+{
+    PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool filt = false;
+    if (i < P.n) {
+        Parsed o;
+        const GAcc R{P.recs};
+        parse_record(R, P, P.offs[i], o);
+        uint32_t words = 0, a[4] = {0, 0, 0, 0};
+        if (o.dir == 2) filt = true;
+        else if (o.has4) {
+            a[0] = __builtin_bswap32(R.u32(o.dir == 0 ? o.v4 + 12 : o.v4 + 16));
+            words = 1;
+        } else if (o.has6) {
+            const uint64_t at = o.dir == 0 ? o.v6 + 8 : o.v6 + 24;
+            for (int k = 0; k < 4; k++) a[k] = __builtin_bswap32(R.u32(at + 4 * k));
+            words = 4;
+        }
+        for (int k = 0; k < 2 && words && !filt; k++) {
+            const uint8_t *pass = k ? pass_asn : pass_city;
+            if (!pass || !G.tree[k]) continue;
+            uint32_t id = 0;
+            if (words == 1 || G.ip_version[k] == 6) {
+                uint32_t t = words == 1 ? G.start4[k] : (G.node_count[k] ? 0u : PV_GEO_LEAF);
+                for (uint32_t q = 0; q < words; q++) t = pv_geo_step32(G.tree[k], G.node_count[k], t, a[q]);
+                id = pv_geo_id(t);
+            }
+            if (id >= G.entries[k]) id = 0;
+            if (!pass[id]) filt = true;
+        }
+    }
+    const uint64_t m = __ballot(filt);
+    if ((threadIdx.x & 63) == 0 && (i & ~63ull) < P.n) out[i >> 6] = m;
 }

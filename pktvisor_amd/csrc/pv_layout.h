@@ -492,6 +492,9 @@ struct PvParams {
     // deep sampling (deep_sample_rate < 100, AbstractMetricsManager::new_event): bit i set =
     // record i's Net event / DNS event draws "not deep" (the managers' jsf32 draws, on the host)
     const PV_G uint32_t *ndeep_net, *ndeep_dns;
+    // Net geo filters on attached databases (pv_set_net_filters): bit i set = record i is a
+    // filtered Net event (pv_geo_verdict writes it, the general Net pass reads it); null = none
+    const PV_G uint64_t *gfilt;
     uint32_t dpos[PV_MAX_SHIFTS];      // span-relative ord of the event that shifts DNS period k+1
     PV_G const uint32_t *psl;          // public_suffix_list table (PVDF_PSL)
 };

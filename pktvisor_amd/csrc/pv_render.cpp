@@ -86,6 +86,27 @@ int read_topn(pv_ctx *c, uint32_t s, std::vector<TopRec> &out) // s: table (PV_T
 // Host-side metric of a top-N entry: its key's metric, or for Net v2 keys a metric per
 // direction (TMH_V2_IP4 + dir, TMH_V2_IP6 + dir)
 enum { TMH_V2_IP4 = 32, TMH_V2_IP6 = 36, TMH_V2_DNS = 64 }; // DNS v2: 64 + 4 * metric + dir
+// top_geo of Net v1 (no device table: dense counts per dictionary id, named from the attached
+// database's dictionary). A top_geoLoc item is the City triple, carried as one name
+// "location \x1f latitude \x1f longitude" (a top_ASN item the same with both empty: the
+// database strings are UTF-8 text, unlike DNS names, which are raw packet bytes and stay escaped
+// byte-wise) so equal triples fold wherever names fold (window
+// merges, external buckets from contexts with other databases); geo_item splits it again.
+enum { TMH_GEO_LOC = 40, TMH_GEO_ASN = 41 };
+#define PV_GEO_SEP '\x1f'
+// (split from the right: latitude and longitude are "%f" renderings and hold no separator, so a
+// location string may hold any byte; only lists the caller marks as geo are split at all)
+static bool geo_item(const std::string &name, std::string &loc, std::string &lat, std::string &lon)
+{
+    const size_t b = name.rfind(PV_GEO_SEP);
+    if (b == std::string::npos || b == 0) return false;
+    const size_t a = name.rfind(PV_GEO_SEP, b - 1);
+    if (a == std::string::npos) return false;
+    loc = name.substr(0, a);
+    lat = name.substr(a + 1, b - a - 1);
+    lon = name.substr(b + 1);
+    return true;
+}
 uint32_t host_metric(const pv_ctx *c, uint64_t key)
 {
     if (PV_IS_V2_IP4(key)) return TMH_V2_IP4 + (uint32_t)((key >> 34) & 3);
@@ -247,6 +268,22 @@ int load_bucket(pv_ctx *c, const std::vector<uint32_t> &slots, bool merged, int 
             if (rc) return rc;
             for (auto &r : recs) b.tops[host_metric(c, r.key)][r.name] += r.count;
         }
+        if (part == PART_NET)
+            for (int k = 0; k < 2; k++) {
+                // top_geo: the slot's exact counts per dictionary id, by rendered string
+                const pv_ctx::GeoAttach &g = c->geo[k];
+                if (!g.d_cnt || !(c->net_groups & PV_NET_TOP_GEO)) continue;
+                std::vector<uint64_t> cnt(g.dict.size());
+                if (!hip_ok(e = hipMemcpyAsync(cnt.data(), g.d_cnt + (uint64_t)s * cnt.size(), cnt.size() * 8, hipMemcpyDeviceToHost,
+                                               c->stream)) ||
+                    !hip_ok(e = hipStreamSynchronize(c->stream)))
+                    return c->hipfail(e, "read geo counts");
+                for (size_t i = 0; i < cnt.size(); i++) {
+                    if (!cnt[i]) continue;
+                    const pv_geodb::Entry &en = g.dict[i];
+                    b.tops[k == 0 ? TMH_GEO_LOC : TMH_GEO_ASN][en.name + PV_GEO_SEP + en.lat + PV_GEO_SEP + en.lon] += cnt[i];
+                }
+            }
         if (part != PART_DNS) continue;
         const uint32_t sg = s | (c->gen[s] << 8);
         if (c->xq_on) continue; // (the merged view's values: after the loop, for the slot set)
@@ -278,7 +315,8 @@ int load_bucket(pv_ctx *c, const std::vector<uint32_t> &slots, bool merged, int 
 // TopN::to_json (src/Metrics.h:577-590): the first topn_count items by estimate, cut at the
 // first one below the topn_percentile_threshold quantile of those estimates (_get_threshold,
 // :510-521, the KLL inclusive rank rule on them)
-void top_json(Json &j, const char *key, const std::vector<std::pair<std::string, uint64_t>> &v0, size_t n, uint32_t pct)
+void top_json(Json &j, const char *key, const std::vector<std::pair<std::string, uint64_t>> &v0, size_t n, uint32_t pct,
+              bool geo = false)
 {
     auto v = v0;
     std::sort(v.begin(), v.end(), [](const auto &a, const auto &b) {
@@ -298,7 +336,12 @@ void top_json(Json &j, const char *key, const std::vector<std::pair<std::string,
     j.arr();
     for (size_t i = 0; i < k && v[i].second >= thr; i++) {
         j.obj();
-        j.key("name").str(v[i].first);
+        std::string loc, lat, lon;
+        if (geo && geo_item(v[i].first, loc, lat, lon)) {
+            // TopN<City>::to_json's formatter (net/v1/NetStreamHandler.cpp:493-500)
+            j.key("name").text(loc);
+            if (!lat.empty() && !lon.empty()) { j.key("lat").str(lat); j.key("lon").str(lon); }
+        } else j.key("name").str(v[i].first);
         j.key("estimate").u(v[i].second);
         j.end_obj();
     }
@@ -416,8 +459,9 @@ void net_json(pv_ctx *c, Json &j, const HostBucket &b)
         top_json(j, "top_ipv6", tops_of(b, TM_IPV6), topn, pct);
     }
     if (c->net_groups & PV_NET_TOP_GEO) {
-        j.key("top_geoLoc").arr(); j.end_arr();
-        j.key("top_ASN").arr(); j.end_arr();
+        // (empty without a database: _process_geo_metrics updates neither TopN)
+        top_json(j, "top_geoLoc", tops_of(b, TMH_GEO_LOC), topn, pct, true);
+        top_json(j, "top_ASN", tops_of(b, TMH_GEO_ASN), topn, pct, true);
     }
     uint64_t cnt;
     auto q = hist_quantiles(&b.sum[PV_OFF_PAYLOAD], PV_PAYLOAD_BINS, cnt);
@@ -687,7 +731,7 @@ struct Prom {
     }
     // TopN::to_prometheus: the to_json selection, one sample per item labelled item_key=name
     void topn(const std::string &name, const char *item_key, const char *desc,
-              const std::vector<std::pair<std::string, uint64_t>> &v0, size_t n, uint32_t pct)
+              const std::vector<std::pair<std::string, uint64_t>> &v0, size_t n, uint32_t pct, bool geo = false)
     {
         auto v = v0;
         std::sort(v.begin(), v.end(), [](const auto &a, const auto &b) {
@@ -704,7 +748,13 @@ struct Prom {
         head(name, desc, "gauge");
         PromLabels l(add);
         for (size_t i = 0; i < k && v[i].second >= thr; i++) {
-            l[item_key] = v[i].first;
+            std::string loc, lat, lon;
+            if (geo && geo_item(v[i].first, loc, lat, lon)) {
+                // the City formatter (net/v1/NetStreamHandler.cpp:377-383): lat / lon are set when
+                // both are there and, the label map being one for all items, stay until replaced
+                l[item_key] = loc;
+                if (!lat.empty() && !lon.empty()) { l["lat"] = lat; l["lon"] = lon; }
+            } else l[item_key] = v[i].first;
             o << name << lbl(l) << ' ' << v[i].second << '\n';
         }
     }
@@ -832,7 +882,7 @@ struct Otlp {
     }
     // TopN: one gauge point per reported item (items with an empty name are skipped)
     void topn(const std::string &name, const char *item_key, const char *desc,
-              const std::vector<std::pair<std::string, uint64_t>> &v0, size_t n, uint32_t pct)
+              const std::vector<std::pair<std::string, uint64_t>> &v0, size_t n, uint32_t pct, bool geo = false)
     {
         auto v = v0;
         std::sort(v.begin(), v.end(), [](const auto &a, const auto &b) {
@@ -851,7 +901,11 @@ struct Otlp {
         bool any = false;
         for (size_t i = 0; i < k && v[i].second >= thr; i++) {
             if (v[i].first.empty()) continue;
-            l[item_key] = v[i].first;
+            std::string loc, lat, lon;
+            if (geo && geo_item(v[i].first, loc, lat, lon)) { // (:434-440, as in the Prometheus form)
+                l[item_key] = loc;
+                if (!lat.empty() && !lon.empty()) { l["lat"] = lat; l["lon"] = lon; }
+            } else l[item_key] = v[i].first;
             g.bytes(1, number_point(l, (int64_t)v[i].second));
             any = true;
         }
@@ -924,7 +978,11 @@ void net_metrics(pv_ctx *c, Sink &p, const HostBucket &b)
         p.topn("packets_top_ipv4", "ipv4", "Top IPv4 IP addresses", tops_of(b, TM_IPV4), topn, pct);
         p.topn("packets_top_ipv6", "ipv6", "Top IPv6 IP addresses", tops_of(b, TM_IPV6), topn, pct);
     }
-    // top_geo: no MaxMind database, the TopNs stay empty and write nothing
+    if (c->net_groups & PV_NET_TOP_GEO) {
+        // (without a database the TopNs stay empty and write nothing)
+        p.topn("packets_top_geoLoc", "geo_loc", "Top GeoIP locations", tops_of(b, TMH_GEO_LOC), topn, pct, true);
+        p.topn("packets_top_ASN", "asn", "Top ASNs by IP", tops_of(b, TMH_GEO_ASN), topn, pct, true);
+    }
     uint64_t cnt;
     const uint64_t *h = &b.sum[PV_OFF_PAYLOAD];
     auto q = hist_quantiles(h, PV_PAYLOAD_BINS, cnt);

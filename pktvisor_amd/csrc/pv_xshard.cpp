@@ -970,6 +970,9 @@ int pv_window_regions(pv_ctx *c, pv_region *r, uint32_t max, uint32_t *n)
         sum(s, 0, PV_OFF_NET2);
         cpc(s, CPC_SRC, CPC_V2);
         if (c->net2_groups) { sum(s, PV_OFF_NET2, PV_SUM_NET_WORDS); cpc(s, CPC_V2, CPC_QNAME); }
+        // the slot's geo counts (ranks attach identical databases: the dictionary ids are a function of the file)
+        for (auto &g : c->geo)
+            if (g.d_cnt) v.push_back(pv_region{g.d_cnt + (size_t)s * g.dict.size(), g.dict.size(), PV_REDUCE_SUM, 0});
         c->net.clean[s] = false;
     }
     for (uint32_t s : c->dns.slots) {
@@ -1025,6 +1028,15 @@ int pv_comm_allreduce_window(pv_ctx *c)
     std::lock_guard<std::mutex> g(c->mu);
     hipSetDevice(c->device);
     flush_fills(c);
+    if (c->geo[0].on || c->geo[1].on) {
+        // the geo counts are summed id by id: every rank must have attached the same databases
+        const uint64_t mine[2] = {c->geo[0].on ? c->geo[0].hash : 0, c->geo[1].on ? c->geo[1].hash : 0};
+        std::vector<uint8_t> all;
+        if (int rc = comm_allgather_locked(c, mine, sizeof mine, all)) return rc;
+        for (int k = 0; k < c->comm_ranks; k++)
+            if (memcmp(all.data() + (size_t)k * sizeof mine, mine, sizeof mine))
+                return c->fail(PV_EINVAL, "geo databases differ across ranks (rank %d holds others than rank %d)", k, c->comm_rank);
+    }
     ncclResult_t r = ncclGroupStart();
     for (uint32_t i = 0; i < n && r == ncclSuccess; i++)
         r = ncclAllReduce(v[i].ptr, v[i].ptr, v[i].words, v[i].op == PV_REDUCE_SUM ? ncclUint64 : ncclInt64,

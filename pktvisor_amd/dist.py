@@ -195,10 +195,13 @@ def check_aligned(handlers, group=None, comm=None):
     import json
     from pktvisor_amd import PART_DNS, PART_NET
     wins = [handlers.window_periods(PART_NET), handlers.window_periods(PART_DNS)]
-    mine = json.dumps([wins, list(handlers.merge_hints())]).encode()
+    # (the attached GeoIP databases too: the reduce sums their dense counts id by id)
+    mine = json.dumps([wins, list(handlers.merge_hints()), getattr(handlers, "geo_hashes", [0, 0])]).encode()
     allv = [json.loads(v) for v in _allgather(handlers, mine, group, comm)]
     if any(v[0] != allv[0][0] for v in allv):
         raise RuntimeError(f"shard windows differ across ranks: {[v[0] for v in allv]}")
+    if any(v[2] != allv[0][2] for v in allv):
+        raise RuntimeError(f"geo databases differ across ranks (city, asn hashes): {[v[2] for v in allv]}")
     hints = [tuple(int(x) for x in v[1]) for v in allv]
     handlers._merge_hints = hints  # (merge_values, in finalize_window, reads the value counts)
     return hints
