@@ -2256,13 +2256,6 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     P.cb = c->d_cb;
     P.cb_cnt = c->d_cb_cnt;
     P.cb_hm = c->d_cb_cnt + 32768;
-    {
-        // grid ranges per combine workgroup (PV_CB_FAN, A/B runs): fewer, larger tables
-        static const char *fan = getenv("PV_CB_FAN");
-        P.cb_fan = fan ? std::max(1u, std::min(8u, (uint32_t)atoi(fan))) : c->cb_fan;
-        while (P.cb_fan > 1 && (uint64_t)P.cb_fan * P.mq_cap >= (1u << 24)) P.cb_fan--; // run starts are 24-bit
-        P.cb_grid = (grid + P.cb_fan - 1) / P.cb_fan;
-    }
     P.stamps = c->d_stamps;
     P.dq = c->d_dq;
     P.dq_cnt = c->d_dq_cnt;
@@ -2284,6 +2277,24 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     P.ip_base = ((uint64_t)P.slot_of[0] << 60) | ((uint64_t)TM_IPV4 << 56) |
                 ((uint64_t)((c->net_groups & PV_NET_CARDINALITY) ? 1 : 0) << 33);
     const bool tc = (c->dev_net_groups() & PV_NET_TOP_IPS) != 0;
+    {
+        // grid ranges per combine workgroup. A batch of nothing but dense IPv4 entries (the lean
+        // pass with top IPs, no Net v2; the last batch had no DNS message and no deferred record: a
+        // guess, it costs speed only) takes up to three, as many as keep a group within the compact
+        // table's 16-bit record indices, while every CU still gets a workgroup: one table a CU
+        // instead of three (profiles/r8/combine_compact). PV_CB_FAN overrides (A/B runs),
+        // PV_CB_COMPACT=0 keeps every workgroup on the generic table.
+        const char *fan = getenv("PV_CB_FAN"), *cmp = getenv("PV_CB_COMPACT");
+        P.cb_compact = cmp && atoi(cmp) == 0 ? 0u : 1u;
+        uint32_t pick = c->cb_fan;
+        if (P.cb_compact && lean && tc && !c->net2_groups && c->cb_plain) {
+            const uint32_t f = std::min<uint32_t>(3u, 65535u / (P.wt_per_block * 64u));
+            if (f > 1 && (grid + f - 1) / f >= (uint32_t)c->cus) pick = f;
+        }
+        P.cb_fan = fan ? std::max(1u, std::min(8u, (uint32_t)atoi(fan))) : pick;
+        while (P.cb_fan > 1 && (uint64_t)P.cb_fan * P.mq_cap >= (1u << 24)) P.cb_fan--; // run starts are 24-bit
+        P.cb_grid = (grid + P.cb_fan - 1) / P.cb_fan;
+    }
     // PV_NET_KERNEL=span: the span-load pass (top-IPs groups), kept for A/B runs
     const bool span = lean && tc && force && !strcmp(force, "span");
     // both lean passes defer general-path records to pv_net_slow_list
@@ -2404,6 +2415,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         return c->hipfail(e, "kernel execution");
     memcpy(status, c->h_status, sizeof status);
     c->dns_heavy = (uint64_t)status[ST_NDNS] * 2 > n;
+    c->cb_plain = lean && status[ST_NDNS] == 0 && status[ST_NSLOW] == 0;
     if (status[ST_FLAGS] & PVF_NAMES_PENDING) {
         // more created entries than the new-name list holds: their names, before anything reads
         // or purges the tables
@@ -2450,7 +2462,8 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         if (hip_ok(hipMemcpy(tv.data(), c->d_stamps + (1u << 20), tv.size() * 8, hipMemcpyDeviceToHost))) {
             double cs[8] = {0}, ms[8] = {0};
             uint64_t nm = 0;
-            for (uint32_t w = 0; w < grid; w++)
+            const uint32_t cg = P.cb_grid; // combine workgroups (cb_fan grid ranges each)
+            for (uint32_t w = 0; w < cg; w++)
                 for (int k = 0; k < 8; k++) cs[k] += (double)tv[w * 8 + k];
             for (uint32_t w = 0; w < (2u << c->reg_log2); w++) {
                 const uint64_t *m = &tv[65536 + w * 8];
@@ -2460,7 +2473,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
             }
             fprintf(stderr, "pv_tstamps combine (%u wg): init=%.0f insert=%.0f count=%.0f scan=%.0f out=%.0f | merge (%lu wg): "
                             "runs=%.0f load=%.0f insert=%.0f names=%.0f wb=%.0f\n",
-                    grid, cs[0] / grid, cs[1] / grid, cs[2] / grid, cs[3] / grid, cs[4] / grid, (unsigned long)nm,
+                    cg, cs[0] / cg, cs[1] / cg, cs[2] / cg, cs[3] / cg, cs[4] / cg, (unsigned long)nm,
                     ms[0] / std::max<uint64_t>(nm, 1), ms[1] / std::max<uint64_t>(nm, 1), ms[2] / std::max<uint64_t>(nm, 1),
                     ms[3] / std::max<uint64_t>(nm, 1), ms[4] / std::max<uint64_t>(nm, 1));
             hipMemset(c->d_stamps + (1u << 20), 0, tv.size() * 8);

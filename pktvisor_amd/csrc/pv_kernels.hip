@@ -3062,14 +3062,31 @@ __device__ __forceinline__ uint64_t ip_tkey(uint64_t e)
 #ifndef PV_CB_U
 #define PV_CB_U 8 // tuning: dense IP log loads in flight per combine thread
 #endif
+#ifndef PV_CB_OSWEEP
+#define PV_CB_OSWEEP 4 // tuning: sweeps of the compact out pass, each a part of the regions
+#endif
 #ifndef PV_MG_U
 #define PV_MG_U 8 // tuning: run entries in flight per merge thread
 #endif
 template <uint32_t CN, uint32_t NR>
 struct CombState {
-    alignas(16) uint64_t key[CN];
-    uint32_t cnt[CN];
-    uint32_t rep[CN];
+    union {
+        struct {
+            alignas(16) uint64_t key[CN];
+            uint32_t cnt[CN];
+            uint32_t rep[CN];
+        };
+        // compact mode (a workgroup whose ranges hold dense v1 IPv4 entries only): twice the
+        // slots in the same bytes. The key is the address (0: empty); a slot's parity is the
+        // direction bit ^ the address's bit parity, so (address, direction) is the key and one
+        // direction alone still fills both halves. Counts and smallest record indices
+        // (relative to the group's first record) are 16-bit halves, two slots a word.
+        struct {
+            alignas(16) uint32_t ckey[2 * CN];
+            uint32_t ccnt[CN];
+            uint32_t crep[CN];
+        };
+    };
     uint32_t h[NR];   // entries per region, then the placement cursors
     uint32_t tb[NR / 2]; // tables among each region's entries (16 bits a region: the run word's
                          // folded PV_TSLOT bit), two regions a word
@@ -3090,12 +3107,13 @@ __device__ __forceinline__ ulonglong2 comb_entry(uint64_t ck, uint32_t w, uint32
     return make_ulonglong2(e0, (uint64_t)w | ((uint64_t)rep << 32));
 }
 template <class St>
-__device__ __forceinline__ void comb_count(PV_CREF(PvParams) P, St &S, uint64_t e0)
+__device__ __forceinline__ uint32_t comb_count(PV_CREF(PvParams) P, St &S, uint64_t e0)
 {
     const uint32_t r = run_key(P, e0);
     atomicAdd(&S.h[r], 1u);
     const uint32_t bit = 1u << ((entry_table(e0) & 15u) + 16u * (r & 1u));
     if (!(S.tb[r >> 1] & bit)) atomicOr(&S.tb[r >> 1], bit);
+    return r;
 }
 #ifndef PV_CB_BUCKET
 #define PV_CB_BUCKET 1 // probe aligned 4-entry buckets (two 16-B LDS reads each), at most 4 (0: 16 dependent
@@ -3202,6 +3220,83 @@ __device__ __forceinline__ void comb_add_pre(PV_CREF(PvParams) P, St &S, PV_G ul
     comb_spill(P, S, sp, ck, w, rep);
 }
 
+// ---- compact mode (CombState's second view; CN2 slots)
+// slot of (address, direction): a 32-bit hash of the address (murmur3's finaliser), its low bit
+// replaced by the direction bit ^ the address's bit parity
+__device__ __forceinline__ uint32_t comb_hash32(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x85ebca6bu;
+    x ^= x >> 13;
+    x *= 0xc2b2ae35u;
+    return x ^ (x >> 16);
+}
+template <uint32_t CN2>
+__device__ __forceinline__ uint32_t comb_cpos(uint32_t ip, uint32_t dir)
+{
+    return (comb_hash32(ip) & (CN2 - 2u)) | (((uint32_t)__popc(ip) ^ dir) & 1u);
+}
+// one more record of compact slot pos: its count half (no carry: a group holds at most 65,535
+// records) and, when the record's relative index rel is below the pre-read rel0, its index half
+template <class St>
+__device__ __forceinline__ void comb_chit(St &S, uint32_t pos, uint32_t rel, uint32_t rel0)
+{
+    const uint32_t sh = 16u * (pos & 1u);
+    atomicAdd(&S.ccnt[pos >> 1], 1u << sh);
+    if (rel < rel0) {
+        uint32_t old = S.crep[pos >> 1];
+        while (rel < ((old >> sh) & 0xffffu)) {
+            const uint32_t prev = atomicCAS(&S.crep[pos >> 1], old, (old & ~(0xffffu << sh)) | rel << sh);
+            if (prev == old) break;
+            old = prev;
+        }
+    }
+}
+// one aligned 8-slot bucket (two 16-B LDS reads), its four slots of parity par: match or claim
+// (one claim and one hit site in a loop over a bucket's slots was measured and is slower: C2
+// insert phase 110.6K -> 120K cycles, profiles/r8/combine_compact)
+template <class St>
+__device__ __forceinline__ bool comb_cbucket(St &S, uint32_t b, uint32_t par, uint32_t ip, uint32_t rel)
+{
+    const uint4 *kp = reinterpret_cast<const uint4 *>(&S.ckey[b]);
+    const uint4 lo = kp[0], hi = kp[1];
+    const uint32_t cur4[4] = {par ? lo.y : lo.x, par ? lo.w : lo.z, par ? hi.y : hi.x, par ? hi.w : hi.z};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t s = b + 2u * j + par;
+        uint32_t cur = cur4[j];
+        if (cur == 0) {
+            const uint32_t prev = atomicCAS(&S.ckey[s], 0u, ip);
+            cur = prev == 0 ? ip : prev;
+        }
+        if (cur == ip) {
+            comb_chit(S, s, rel, 0xffffffffu);
+            return true;
+        }
+    }
+    return false;
+}
+// record base + rel of (ip, dir) into the compact table, the first probe's key and index half
+// pre-read (cur0 / rel0); then the aligned buckets after the slot's own; else the spill list
+template <uint32_t CN2, class St>
+__device__ __forceinline__ void comb_cadd_pre(PV_CREF(PvParams) P, St &S, PV_G ulonglong2 *sp, uint32_t ip, uint32_t dir,
+                                              uint32_t base, uint32_t rel, uint32_t pos, uint32_t cur0, uint32_t rel0)
+{
+    uint32_t cur = cur0;
+    if (cur == 0) {
+        const uint32_t prev = atomicCAS(&S.ckey[pos], 0u, ip);
+        cur = prev == 0 ? ip : prev;
+        rel0 = 0xffffffffu;
+    }
+    if (cur == ip) {
+        comb_chit(S, pos, rel, rel0);
+        return;
+    }
+    for (uint32_t g = 1; g <= 4; g++)
+        if (comb_cbucket(S, ((pos & ~7u) + 8u * g) & (CN2 - 1), pos & 1u, ip, rel)) return;
+    comb_spill(P, S, sp, P.ip_base | (uint64_t)dir << 32 | ip, 1u, base + rel);
+}
+
 // exclusive prefix of v over the workgroup (all threads call it); *total = the sum
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, uint32_t &total)
 {
@@ -3232,20 +3327,76 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
     __shared__ St S;
     TST_DECL
     const uint32_t nreg = 2u << P.reg_log2; // run keys
-    for (uint32_t j = threadIdx.x; j < CN; j += blockDim.x) { S.key[j] = 0; S.cnt[j] = 0; S.rep[j] = 0xffffffffu; }
-    for (uint32_t r = threadIdx.x; r < nreg; r += blockDim.x) {
-        S.h[r] = 0;
-        if (!(r & 1)) S.tb[r >> 1] = 0;
-    }
-    if (threadIdx.x == 0) S.nsp = 0;
-    __syncthreads();
-    TST(0)
     // this workgroup's grid ranges [g0, g1) (cb_fan of them): their update logs and IP logs into
     // one table, one list at the first range's place
     const uint32_t g0 = blockIdx.x * P.cb_fan, g1 = min(g0 + P.cb_fan, P.grid_main);
     const uint64_t wbase = (uint64_t)g0 * P.mq_cap;
     PV_G ulonglong2 *sp = reinterpret_cast<PV_G ulonglong2 *>(P.tp_buf) + wbase;
     PV_G ulonglong2 *out = reinterpret_cast<PV_G ulonglong2 *>(P.cb) + wbase;
+    // compact mode: the ranges hold nothing but the compact IP log's dense IPv4 entries (no
+    // update-log entry, no exception entry) of at most 65,535 records; the same for every thread.
+    // Only a workgroup of more than one range takes it: with one range the compact table was
+    // measured no faster than the generic one (61.2K against 60.6K cycles a C2 workgroup, the
+    // insert's gain spent on the count pass over twice the slots; profiles/r8/combine_compact)
+    constexpr uint32_t CK = 16; // compact slots a thread of a full workgroup
+    constexpr bool CAN = CN * 2 == CK * PV_CB_THREADS && NR <= 2048;
+    // (the counts are read here and looked at after the table is cleared: the same words clear
+    // either view)
+    uint32_t cbase = 0; // the group's first record
+    uint32_t other = 1;
+    if constexpr (CAN) {
+        if (P.cb_compact && g1 - g0 > 1 && P.ip_compact && (P.net_groups & PV_NET_TOP_IPS_BIT) && blockDim.x == PV_CB_THREADS) {
+            uint64_t a0, z0, a1, z1;
+            wg_records(P, g0, a0, z0);
+            wg_records(P, g1 - 1, a1, z1);
+            other = z1 - a0 > 65535 ? 1u : 0u;
+            for (uint32_t gr = g0; gr < g1; gr++) other |= P.mq_cnt[gr] | P.ipx_cnt[gr];
+            cbase = (uint32_t)a0;
+        }
+    }
+    for (uint32_t j = threadIdx.x; j < CN; j += blockDim.x) { S.key[j] = 0; S.cnt[j] = 0; S.rep[j] = 0xffffffffu; }
+    for (uint32_t r = threadIdx.x; r < nreg; r += blockDim.x) {
+        S.h[r] = 0;
+        if (!(r & 1)) S.tb[r >> 1] = 0;
+    }
+    if (threadIdx.x == 0) S.nsp = 0;
+    const bool compact = CAN && __builtin_amdgcn_readfirstlane(other) == 0;
+    __syncthreads();
+    TST(0)
+    if (compact) {
+        if constexpr (CAN) {
+            // the generic compact-log loop below with 4-B keys: PV_CB_U log words and direction
+            // words in flight, then every first-probe key and index half, then the inserts
+            const PV_G uint32_t *ip4 = P.iplog32;
+            for (uint32_t gr = g0; gr < g1; gr++) {
+                uint64_t a, z;
+                wg_records(P, gr, a, z);
+                const uint32_t nn = (uint32_t)(z - a), bd = blockDim.x, ra = (uint32_t)(a - cbase);
+                for (uint32_t j0 = threadIdx.x; j0 < nn; j0 += PV_CB_U * bd) {
+                    uint32_t ipv[PV_CB_U];
+                    uint64_t dw[PV_CB_U];
+#pragma unroll
+                    for (int u = 0; u < PV_CB_U; u++) {
+                        const uint32_t j = j0 + u * bd;
+                        ipv[u] = j < nn ? ip4[a + j] : 0u;
+                        dw[u] = j < nn ? P.ipdir[(a + j) >> 6] : 0ull;
+                    }
+                    uint32_t dir[PV_CB_U], pos[PV_CB_U], cur[PV_CB_U], rp[PV_CB_U];
+#pragma unroll
+                    for (int u = 0; u < PV_CB_U; u++) {
+                        const uint64_t r = a + j0 + (uint64_t)u * bd;
+                        dir[u] = (uint32_t)(dw[u] >> (r & 63)) & 1u;
+                        pos[u] = comb_cpos<2 * CN>(ipv[u], dir[u]);
+                        cur[u] = ipv[u] ? S.ckey[pos[u]] : 0u;
+                        rp[u] = ipv[u] ? (S.crep[pos[u] >> 1] >> (16u * (pos[u] & 1u))) & 0xffffu : 0u;
+                    }
+#pragma unroll
+                    for (int u = 0; u < PV_CB_U; u++)
+                        if (ipv[u]) comb_cadd_pre<2 * CN>(P, S, sp, ipv[u], dir[u], cbase, ra + j0 + u * bd, pos[u], cur[u], rp[u]);
+                }
+            }
+        }
+    } else
     for (uint32_t gr = g0; gr < g1; gr++) {
     const uint32_t cnt = P.mq_cnt[gr];
     const PV_G uint64_t *q = P.mq + (uint64_t)gr * P.mq_cap * 2;
@@ -3303,6 +3454,19 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
     // an entry where its CAS claims it instead was measured and is slower: the claiming lanes are
     // a fifth of a wave there (C2 insert phase 37.5K -> 56.3K cycles for this pass's 6.4K,
     // profiles/r7/topn_seen)
+    // (compact mode: a thread's CK slots' run keys stay in registers, two a word, for the out pass)
+    uint32_t rk[CK / 2] = {};
+    if (compact) {
+        if constexpr (CAN) {
+            const uint64_t tk = P.ip_base & (0xffull << 56); // an IPv4 table key's slot and metric bits
+#pragma unroll
+            for (uint32_t k = 0; k < CK; k++) {
+                const uint32_t ip = S.ckey[threadIdx.x + k * PV_CB_THREADS];
+                const uint32_t r = ip ? comb_count(P, S, tk | ip) : 0u;
+                rk[k / 2] = k & 1 ? rk[k / 2] | r << 16 : r;
+            }
+        }
+    } else
     for (uint32_t j = threadIdx.x; j < CN; j += blockDim.x)
         if (S.key[j]) comb_count(P, S, comb_entry(S.key[j], S.cnt[j], S.rep[j]).x);
     __syncthreads();
@@ -3337,6 +3501,28 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
     }
     lds_barrier(); // the run-table stores are the merge kernel's to read
     TST(3)
+    if (compact) {
+        if constexpr (CAN) {
+            // each slot as the 16-B entry of its (address, direction), the record index absolute
+            // The list is written in PV_CB_OSWEEP sweeps over the slots, each a part of the regions
+            // (the run keys are in registers), so the lines a workgroup has open at a time are a
+            // part of its list: every CU writes its whole group's list at once here, and one
+            // sweep over all regions took 41.0K cycles on C2, two 36.4K, four 27.0K
+            // (profiles/r8/combine_compact)
+#pragma unroll 1
+            for (uint32_t q = 0; q < PV_CB_OSWEEP; q++)
+#pragma unroll
+            for (uint32_t k = 0; k < CK; k++) {
+                const uint32_t j = threadIdx.x + k * PV_CB_THREADS, sh = 16u * (j & 1u);
+                const uint32_t ip = S.ckey[j];
+                if (!ip) continue;
+                if (PV_CB_OSWEEP > 1 && ((((rk[k / 2] >> (16u * (k & 1u))) & 0xffffu) * PV_CB_OSWEEP) >> P.reg_log2) != q) continue;
+                const uint64_t ck = P.ip_base | (uint64_t)((j ^ (uint32_t)__popc(ip)) & 1u) << 32 | ip;
+                const ulonglong2 e = comb_entry(ck, (S.ccnt[j >> 1] >> sh) & 0xffffu, cbase + ((S.crep[j >> 1] >> sh) & 0xffffu));
+                out[atomicAdd(&S.h[(rk[k / 2] >> (16u * (k & 1u))) & 0xffffu], 1u)] = e;
+            }
+        }
+    } else
     for (uint32_t j = threadIdx.x; j < CN; j += blockDim.x)
         if (S.key[j]) {
             const ulonglong2 e = comb_entry(S.key[j], S.cnt[j], S.rep[j]);
@@ -3353,8 +3539,8 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
     TST(4)
     TST_FLUSH(0)
 }
-// LDS: an 8192-entry table with up to 2^10 regions per table (152 KiB), 2048 entries with
-// more (128 KiB); two run keys per region
+// LDS: an 8192-entry table (16384 compact slots in the same bytes) with up to 2^10 regions per
+// table, 2048 entries with more; two run keys per region
 #ifndef PV_CB_CN
 #define PV_CB_CN 8192
 #endif

@@ -461,6 +461,7 @@ struct PvParams {
     PV_G uint32_t *cb_hm; // per combine workgroup: handlers with entries (bit 0 Net, 1 DNS); run words of the others unwritten
     uint32_t cb_fan;      // grid ranges per combine workgroup (its list: cb_fan x mq_cap entries)
     uint32_t cb_grid;     // combine workgroups: ceil(grid_main / cb_fan)
+    uint32_t cb_compact;  // combine workgroups whose ranges hold dense v1 IPv4 entries only may take the compact table
     uint32_t xmerge;      // pv_topn_merge over received multi-GPU entries (64-bit weights, no names)
     uint32_t x_lo, x_hi;  // its regions [x_lo, x_hi)
     uint32_t seen_trust;  // record indices have only grown since the last reset: pv_topn_merge may read and
