@@ -676,6 +676,38 @@ typedef struct pv_net_filters {
     const char *const *asn_numbers;  /* digit strings */
 } pv_net_filters;
 int pv_set_net_filters(pv_ctx *ctx, const pv_net_filters *f);
+
+/* ---- The DHCP handler (DhcpStreamHandler, src/handlers/dhcp): the "dhcp" schema next to
+ * "packets" and "dns". While it is attached every batch gets one more device pass
+ * (pv_dhcp_scan: one lane per record, a 64-bit mask per 64-record tile) that finds the DHCP
+ * packets: a UDP packet, as the Net pass sees one, with port 67 / 68 on either side (DHCP), else
+ * 546 / 547 (DHCPv6). They are decoded on the device into an event list in record order
+ * (pv_dhcp_decode), which the host manager replays: its own window (shifted by its own events;
+ * pv_set_start_tstamp, pv_set_end_tstamp and pv_check_period_shift reach it), its own jsf32
+ * deep-sampling draws, the REQUEST / ACK transactions (open ones live across batches), the ten
+ * wire_packets counters and exact top_clients / top_servers. The Net and DNS passes and their
+ * outputs do not change. A batch with more than max_events DHCP packets is decoded in rounds;
+ * nothing is dropped.
+ * Outputs: pv_window_json gains a "dhcp" object (period, wire_packets.{events, deep_samples,
+ * discover, offer, request, ack, solicit, advertise, request_v6, reply, total, filtered},
+ * top_clients, top_servers; filtered is always 0, the handler has no filters; rates are not
+ * kept); pv_window_prometheus takes PV_HANDLER_DHCP.
+ * Refused with PV_EUNSUPPORTED and a message naming DHCP: pv_window_opentelemetry and
+ * pv_bucket_merge with PV_HANDLER_DHCP; pv_process_dnstap while attached (the reference's
+ * "DhcpStreamHandler: unsupported input event proxy"); sharded runs (pktvisor_amd.dist): the
+ * multi-GPU reduce does not carry DHCP state. */
+#define PV_HANDLER_DHCP 4u
+typedef struct pv_dhcp_config {
+    uint32_t xact_ttl_ms;     /* "xact_ttl_ms" / "xact_ttl_secs" * 1000; 0 => 5000 */
+    uint32_t recorded_stream; /* "recorded_stream" (period lengths are the stream's either way) */
+    uint32_t max_events;      /* DHCP events a decode round stores; 0 => min(max_records, 1 << 20) */
+} pv_dhcp_config;
+/* Call before the first batch (or after pv_reset); NULL detaches. Allocates every device buffer of
+ * the stage, so a steady-state batch allocates nothing. */
+int pv_set_dhcp(pv_ctx *ctx, const pv_dhcp_config *cfg);
+/* Device time of pv_dhcp_scan, as pv_kernel_timing gives the Net pass's: summed over the batches
+ * processed while pv_set_kernel_timing is on (every batch's scan is stamped). */
+int pv_dhcp_timing(pv_ctx *ctx, double *scan_ms, uint64_t *launches, int reset);
 /* pv_geodb_hash of the attached city and ASN databases (0: none): what the ranks of a sharded run
  * compare before they sum their windows. pv_comm_allreduce_window compares them itself; a caller
  * that moves the pv_window_regions words with its own transport compares these first. */

@@ -68,6 +68,10 @@ class pv_net_filters(ctypes.Structure):
                 ("n_asn_numbers", ctypes.c_uint32), ("asn_numbers", ctypes.POINTER(ctypes.c_char_p))]
 
 
+class pv_dhcp_config(ctypes.Structure):
+    _fields_ = [("xact_ttl_ms", ctypes.c_uint32), ("recorded_stream", ctypes.c_uint32), ("max_events", ctypes.c_uint32)]
+
+
 from pktvisor_amd.config import ConfigException as ConfigError  # noqa: E402  (the reference's texts)
 from pktvisor_amd.config import StreamHandlerException  # noqa: E402,F401
 
@@ -184,11 +188,12 @@ EXPORTS = ["pv_version", "pv_device_count", "pv_create", "pv_destroy", "pv_last_
            "pv_topn_x_candidates", "pv_topn_x_names", "pv_topn_x_view", "pv_values_x_select", "pv_comm_values_select",
            "pv_slow_x_finish", "pv_comm_slow_finish", "pv_geodb_open", "pv_geodb_open_file", "pv_geodb_close",
            "pv_geodb_last_error", "pv_geodb_entries", "pv_geodb_hash", "pv_geodb_hashes", "pv_set_net_filters", "pv_geodb_entry", "pv_geodb_lookup", "pv_set_geodb",
-           "pv_geodb_lookup_device"]
+           "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing"]
 PV_GEODB_CITY, PV_GEODB_ASN = 0, 1
 # pv_allreduce_fn: (uint64_t *buf, size_t n, int op, void *user) -> int
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
-PV_HANDLER_NET, PV_HANDLER_DNS = 1, 2
+PV_HANDLER_NET, PV_HANDLER_DNS, PV_HANDLER_DHCP = 1, 2, 4
+_HANDLER_BITS = {"net": PV_HANDLER_NET, "dns": PV_HANDLER_DNS, "dhcp": PV_HANDLER_DHCP}
 PV_PERIOD_AUTO = 0xFFFFFFFF
 PART_NET, PART_DNS = 0, 1
 PV_REDUCE_SUM, PV_REDUCE_MIN = 0, 1
@@ -372,6 +377,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.pv_geodb_lookup.argtypes = [P, P, ctypes.c_size_t, U32, P]
     lib.pv_set_geodb.argtypes = [P, P, P]
     lib.pv_geodb_lookup_device.argtypes = [P, U32, P, ctypes.c_size_t, U32, P]
+    lib.pv_set_dhcp.argtypes = [P, ctypes.POINTER(pv_dhcp_config)]
+    lib.pv_dhcp_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.c_int]
     _lib = lib
     return lib
 
@@ -692,7 +699,11 @@ class PvHandlers:
                  dns_config: Optional[dict] = None, topn_percentile_threshold: int = 0,
                  net2_config: Optional[dict] = None, dns2_config: Optional[dict] = None,
                  deep_sample_rate: int = 100, tcp_packet_reassembly_cache_limit: int = 0, bpf=None,
-                 tcp_exact_lru: bool = False, geo_city_db=None, geo_asn_db=None):
+                 tcp_exact_lru: bool = False, geo_city_db=None, geo_asn_db=None, dhcp_config: Optional[dict] = None,
+                 dhcp_max_events: int = 0):
+        """dhcp_config: attaches the DHCP handler ("dhcp" schema, DhcpStreamHandler) with its config
+        map (recorded_stream, xact_ttl_secs, xact_ttl_ms, the window keys); dhcp_max_events: the DHCP
+        events one decode round stores (0: the default)."""
         from pktvisor_amd import config as pvcfg
         self.lib = load_library()
         filt = dns_filter_config(dns_filters) if dns_filters else None
@@ -714,9 +725,10 @@ class PvHandlers:
             self.dnstap_mask = d2["dnstap_mask"]
             if d2["xact_ttl_ms"] is not None:
                 xact_ttl_ms = d2["xact_ttl_ms"]
+        dhcp = pvcfg.dhcp_start(dict(dhcp_config)) if dhcp_config is not None else None
         if net_config is not None or dns_config is not None or net2_config is not None or dns2_config is not None:
             ncfg, dcfg = dict(net_config or {}), dict(dns_config or {})
-            win = pvcfg.window_config([ncfg, dcfg, dict(net2_config or {}), dict(dns2_config or {})])
+            win = pvcfg.window_config([ncfg, dcfg, dict(net2_config or {}), dict(dns2_config or {}), dict(dhcp_config or {})])
             deep_sample_rate = win.get("deep_sample_rate", deep_sample_rate)
             num_periods = win.get("num_periods", num_periods)
             topn_count = win.get("topn_count", topn_count)
@@ -734,6 +746,13 @@ class PvHandlers:
                 self.dnstap_mask = d["dnstap_mask"]
             if d["xact_ttl_ms"] is not None and dns2_config is None:
                 xact_ttl_ms = d["xact_ttl_ms"]
+        elif dhcp_config is not None:
+            # the DHCP handler alone carries window keys: the other handlers keep their keyword form
+            win = pvcfg.window_config([dict(dhcp_config)])
+            deep_sample_rate = win.get("deep_sample_rate", deep_sample_rate)
+            num_periods = win.get("num_periods", num_periods)
+            topn_count = win.get("topn_count", topn_count)
+            topn_percentile_threshold = win.get("topn_percentile_threshold", topn_percentile_threshold)
         self._host = host_spec.encode() if host_spec else None
         cfg = pv_config(self._host, num_periods, topn_count, xact_ttl_ms, net_groups, dns_groups, linktype, ts_nano,
                         device, table_log2, max_records, topn_percentile_threshold, net_filter_all, net2_groups,
@@ -782,6 +801,21 @@ class PvHandlers:
             self.set_geodb(geo_city_db, geo_asn_db)
         if net_filters:
             self.set_net_filters(**net_filters)
+        self.dhcp_attached = False
+        if dhcp is not None:
+            self.set_dhcp(dhcp["xact_ttl_ms"], dhcp["recorded_stream"], dhcp_max_events)
+
+    def set_dhcp(self, xact_ttl_ms: int = 0, recorded_stream: bool = False, max_events: int = 0):
+        """attach the DHCP handler (pv_set_dhcp): window_json then carries "dhcp". Before the first batch."""
+        cfg = pv_dhcp_config(int(xact_ttl_ms), int(bool(recorded_stream)), int(max_events))
+        self._check(self.lib.pv_set_dhcp(self.ctx, ctypes.byref(cfg)), "pv_set_dhcp")
+        self.dhcp_attached = True
+
+    def dhcp_timing(self, reset: bool = False):
+        """(ms, launches) of pv_dhcp_scan over the batches processed while set_kernel_timing is on"""
+        ms, n = ctypes.c_double(), ctypes.c_uint64()
+        self._check(self.lib.pv_dhcp_timing(self.ctx, ctypes.byref(ms), ctypes.byref(n), int(reset)), "pv_dhcp_timing")
+        return ms.value, n.value
 
     def set_net_filters(self, geoloc_notfound=False, asn_notfound=False, only_geoloc_prefix=None, only_asn_number=None):
         """the Net handler's geo filters on the attached databases (pv_set_net_filters); a list of
@@ -907,7 +941,7 @@ class PvHandlers:
         """StreamHandler::merge(bucket, period, prometheus, merged) of handler "net" or "dns":
         a new Bucket when bucket is None, else this handler's bucket folded into it with
         Aggregate::SUM (the same Bucket is returned)."""
-        h = {"net": PV_HANDLER_NET, "dns": PV_HANDLER_DNS}[handler]
+        h = _HANDLER_BITS[handler]
         ptr = ctypes.c_void_p(bucket.ptr if bucket is not None else None)
         self._check(self.lib.pv_bucket_merge(self.ctx, h, ctypes.byref(ptr), period, int(prometheus), int(merged)),
                     "pv_bucket_merge")
@@ -965,9 +999,9 @@ class PvHandlers:
 
     def window_prometheus(self, period: int = 0, labels: Optional[dict] = None, handlers: str = "net,dns") -> str:
         """StreamHandler::window_prometheus (src/AbstractMetricsManager.h:506-531): the
-        Prometheus text of bucket `period` of the named handlers ("net", "dns"), with
+        Prometheus text of bucket `period` of the named handlers ("net", "dns", "dhcp"), with
         `labels` added to every sample."""
-        hmask = sum({"net": 1, "dns": 2}[x] for x in handlers.split(","))
+        hmask = sum(_HANDLER_BITS[x] for x in handlers.split(","))
         labels = labels or {}
         keys = (ctypes.c_char_p * max(1, len(labels)))(*[k.encode() for k in labels])
         vals = (ctypes.c_char_p * max(1, len(labels)))(*[str(v).encode() for v in labels.values()])
@@ -983,7 +1017,7 @@ class PvHandlers:
         protobuf bytes of the ScopeMetrics `metrics` the named handlers add for bucket
         `period`, with `labels` as attributes."""
         labels = labels or {}
-        hmask = sum({"net": 1, "dns": 2}[x] for x in handlers.split(","))
+        hmask = sum(_HANDLER_BITS[x] for x in handlers.split(","))
         keys = (ctypes.c_char_p * max(1, len(labels)))(*[k.encode() for k in labels])
         vals = (ctypes.c_char_p * max(1, len(labels)))(*[str(v).encode() for v in labels.values()])
         out, n = ctypes.c_void_p(), ctypes.c_size_t()

@@ -166,6 +166,24 @@ def net_start(cfg: dict, geo_enabled=None) -> dict:
     return out
 
 
+DHCP_CONFIG_DEFS = ("recorded_stream", "xact_ttl_secs", "xact_ttl_ms")
+
+
+def dhcp_start(cfg: dict) -> dict:
+    """DhcpStreamHandler::start (src/handlers/dhcp/DhcpStreamHandler.cpp:41-69) up to the signal
+    wiring: {"recorded_stream": bool, "xact_ttl_ms": int (0: the TransactionManager's 5000)}.
+    The handler has no metric groups and no filters; xact_ttl_ms wins over xact_ttl_secs."""
+    validate_configs(cfg, DHCP_CONFIG_DEFS)
+    ttl = 0
+    if "xact_ttl_ms" in cfg:
+        ttl = _uint(cfg, "xact_ttl_ms")
+    elif "xact_ttl_secs" in cfg:
+        ttl = _uint(cfg, "xact_ttl_secs") * 1000
+    if ttl > 0xFFFFFFFF:
+        raise ConfigException("wrong type for key: xact_ttl_ms")
+    return {"recorded_stream": "recorded_stream" in cfg, "xact_ttl_ms": ttl}
+
+
 # Net v2 (src/handlers/net/v2/NetStreamHandler.h:25-31,262-267; defaults :47-52)
 NET2_GROUP_DEFS = {"cardinality": 1 << 1, "counters": 1 << 0, "quantiles": 1 << 2, "top_geo": 1 << 3, "top_ips": 1 << 4}
 NET2_DEFAULT_GROUPS = ("counters", "cardinality", "quantiles", "top_geo", "top_ips")

@@ -174,6 +174,9 @@ int ensure_started(pv_ctx *c, int64_t sec, int64_t nsec)
         w.next_shift_sec = sec + 60;
     }
     c->sg_ord[0 | (c->gen[0] << 8)] = 0;
+    // (the DHCP manager hears the input's start_tstamp_signal too: the batch's first record,
+    // not its first DHCP packet)
+    if (c->dhcp) c->dhcp->set_start(sec, nsec);
     c->started = true;
     return 0;
 }
@@ -249,6 +252,7 @@ void mark_merged(pv_ctx *c, const char *by)
     if (!c->merged_by) c->merged_by = by;
 }
 } // namespace pvh
+static void dhcp_free(pv_ctx *c);
 static int merged_refuse(pv_ctx *c)
 {
     if (!c->merged) return 0;
@@ -795,6 +799,7 @@ void pv_destroy(pv_ctx *c)
                     c->d_xcnt, c->d_xrhdr, c->d_xtot, c->d_xsend, c->d_xrecv, c->d_xp, c->d_bpf, c->d_fwork, c->d_frecs,
                     c->d_foffs, c->d_fsc, c->d_fscan, c->d_eoc, c->d_eoc_cnt};
     for (void *p : ptrs) if (p) hipFree(p);
+    dhcp_free(c);
     for (void *p : {(void *)c->d_nf_pass[0], (void *)c->d_nf_pass[1], (void *)c->d_gfilt}) if (p) hipFree(p);
     for (auto &g : c->geo) {
         if (g.d_tree) hipFree(g.d_tree);
@@ -855,6 +860,7 @@ int pv_reset(pv_ctx *c)
         memcpy(w->clean, cl, sizeof cl);
     }
     c->started = c->ended = false;
+    if (c->dhcp) c->dhcp->reset();
     c->records_seen = 0;
     c->seen_hi = 0; // (every slot is cleared before its next use: no entry keeps a seen flag)
     c->seen_off = false;
@@ -2675,6 +2681,114 @@ int bpf_filter_device(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, 
     return 0;
 }
 
+// The DHCP handler's device stage on a batch (pv_dhcp.hip) and the host replay of what it finds:
+// the scan's per-tile masks and counts, their exclusive scan (each tile's rank base), then rounds
+// of at most dhcp_cap events: decode, copy back, replay in record order. Nothing is dropped: a
+// batch with more events than a round holds takes more rounds. The caller holds c->mu.
+static int dhcp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, const pv_index_info *info, hipStream_t st)
+{
+    hipError_t e;
+    const uint32_t n = (uint32_t)info->n_records, ntiles = (n + 63) / 64;
+    size_t tb = 0;
+    if (!hip_ok(e = pv_exclusive_scan_u32(nullptr, &tb, nullptr, nullptr, ntiles, st))) return c->hipfail(e, "DHCP scan size");
+    if (int rc = x_grow_dev(c, &c->d_dh_scan, c->dh_scan_bytes, tb, "DHCP scan")) return rc;
+    const uint32_t grid = std::max(1u, std::min((ntiles + 3) / 4, (uint32_t)c->cus * 8));
+    const bool timed = c->timing_every != 0;
+    if (timed) hipEventRecord(c->ev_start, st);
+    hipLaunchKernelGGL(pv_dhcp_scan, dim3(grid), dim3(256), 0, st, d_recs, d_offs, n, c->cfg.linktype, c->cfg.ts_nano,
+                       (const PvParams *)c->d_dh_params, c->d_dh_mask, c->d_dh_cnt);
+    if (!hip_ok(e = hipGetLastError())) return c->hipfail(e, "launch pv_dhcp_scan");
+    if (timed) hipEventRecord(c->ev_stop, st);
+    tb = c->dh_scan_bytes;
+    uint32_t tail[2] = {0, 0};
+    if (!hip_ok(e = pv_exclusive_scan_u32(c->d_dh_scan, &tb, c->d_dh_cnt, c->d_dh_rank, ntiles, st)) ||
+        !hip_ok(e = hipMemcpyAsync(&tail[0], c->d_dh_rank + ntiles - 1, 4, hipMemcpyDeviceToHost, st)) ||
+        !hip_ok(e = hipMemcpyAsync(&tail[1], c->d_dh_cnt + ntiles - 1, 4, hipMemcpyDeviceToHost, st)) ||
+        !hip_ok(e = hipStreamSynchronize(st)))
+        return c->hipfail(e, "DHCP scan");
+    if (timed) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->ev_start, c->ev_stop) == hipSuccess) { c->dhcp_scan_ms += ms; c->dhcp_scan_launches++; }
+    }
+    const uint32_t total = tail[0] + tail[1];
+    for (uint32_t base = 0; base < total; base += c->dhcp_cap) {
+        const uint32_t k = std::min(c->dhcp_cap, total - base);
+        uint32_t top = 0;
+        if (!hip_ok(e = hipMemsetAsync(c->d_dh_top, 0, 4, st))) return c->hipfail(e, "DHCP decode");
+        hipLaunchKernelGGL(pv_dhcp_decode, dim3((n + 255) / 256), dim3(256), 0, st, d_recs, d_offs, n, c->cfg.linktype,
+                           c->cfg.ts_nano, (const PvParams *)c->d_dh_params, (const unsigned long long *)c->d_dh_mask,
+                           (const uint32_t *)c->d_dh_rank, base, c->dhcp_cap, c->d_dh_ev, c->d_dh_arena,
+                           c->dhcp_cap * PV_DHCP_HOST_MAX, c->d_dh_top);
+        if (!hip_ok(e = hipGetLastError())) return c->hipfail(e, "launch pv_dhcp_decode");
+        c->h_dh_ev.resize(k);
+        if (!hip_ok(e = hipMemcpyAsync(c->h_dh_ev.data(), c->d_dh_ev, (size_t)k * sizeof(PvDhcpEvent), hipMemcpyDeviceToHost, st)) ||
+            !hip_ok(e = hipMemcpyAsync(&top, c->d_dh_top, 4, hipMemcpyDeviceToHost, st)) || !hip_ok(e = hipStreamSynchronize(st)))
+            return c->hipfail(e, "DHCP events");
+        top = std::min(top, c->dhcp_cap * PV_DHCP_HOST_MAX);
+        c->h_dh_arena.resize(top);
+        // (hostnames: REQUEST messages only; most rounds have none and stop at the one synchronize)
+        if (top && !hip_ok(e = hipMemcpy(c->h_dh_arena.data(), c->d_dh_arena, top, hipMemcpyDeviceToHost)))
+            return c->hipfail(e, "DHCP hostnames");
+        c->dhcp->replay(c->h_dh_ev.data(), k, c->h_dh_arena.data(), top);
+    }
+    return 0;
+}
+
+static void dhcp_free(pv_ctx *c)
+{
+    for (void *p : {(void *)c->d_dh_mask, (void *)c->d_dh_cnt, (void *)c->d_dh_rank, (void *)c->d_dh_top, (void *)c->d_dh_ev,
+                    (void *)c->d_dh_arena, (void *)c->d_dh_params, c->d_dh_scan})
+        if (p) hipFree(p);
+    c->d_dh_mask = nullptr;
+    c->d_dh_cnt = c->d_dh_rank = c->d_dh_top = nullptr;
+    c->d_dh_ev = nullptr;
+    c->d_dh_arena = nullptr;
+    c->d_dh_params = nullptr;
+    c->d_dh_scan = nullptr;
+    c->dh_scan_bytes = 0;
+    c->dhcp.reset();
+}
+
+// DhcpStreamHandler's constructor and start() (DhcpStreamHandler.cpp:9-69) on this context's pcap
+// input: the manager with the context's window config, and every device buffer of the stage
+extern "C" int pv_set_dhcp(pv_ctx *c, const pv_dhcp_config *cfg)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    if (c->started) return c->fail(PV_EINVAL, "pv_set_dhcp: call before the first batch");
+    hipSetDevice(c->device);
+    dhcp_free(c);
+    if (!cfg) return 0;
+    c->dhcp_cfg = *cfg;
+    const uint64_t maxn = std::max<uint64_t>(1, c->max_records);
+    uint64_t cap = cfg->max_events ? cfg->max_events : std::min<uint64_t>(maxn, 1u << 20);
+    cap = std::min<uint64_t>(cap, 1u << 22); // (the hostname arena's 32-bit offsets: cap * 255 bytes)
+    c->dhcp_cap = (uint32_t)cap;
+    const size_t ntiles = (size_t)((maxn + 63) / 64);
+    hipError_t e;
+    size_t tb = 0;
+    if (!hip_ok(e = hipMalloc(&c->d_dh_mask, ntiles * 8)) || !hip_ok(e = hipMalloc(&c->d_dh_cnt, ntiles * 4)) ||
+        !hip_ok(e = hipMalloc(&c->d_dh_rank, ntiles * 4)) || !hip_ok(e = hipMalloc(&c->d_dh_top, 256)) ||
+        !hip_ok(e = hipMalloc(&c->d_dh_ev, cap * sizeof(PvDhcpEvent))) ||
+        !hip_ok(e = hipMalloc(&c->d_dh_arena, cap * PV_DHCP_HOST_MAX)) || !hip_ok(e = hipMalloc(&c->d_dh_params, sizeof(PvParams))) ||
+        !hip_ok(e = hipMemset(c->d_dh_params, 0, sizeof(PvParams))) ||
+        !hip_ok(e = pv_exclusive_scan_u32(nullptr, &tb, nullptr, nullptr, ntiles, c->stream))) {
+        dhcp_free(c);
+        return c->hipfail(e, "DHCP stage buffers");
+    }
+    if (int rc = x_grow_dev(c, &c->d_dh_scan, c->dh_scan_bytes, tb, "DHCP scan")) { dhcp_free(c); return rc; }
+    c->dhcp.reset(new pvdhcp::Manager(c->cfg.num_periods, c->cfg.deep_sample_rate, cfg->xact_ttl_ms));
+    return 0;
+}
+
+extern "C" int pv_dhcp_timing(pv_ctx *c, double *scan_ms, uint64_t *launches, int reset)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    if (scan_ms) *scan_ms = c->dhcp_scan_ms;
+    if (launches) *launches = c->dhcp_scan_launches;
+    if (reset) { c->dhcp_scan_ms = 0; c->dhcp_scan_launches = 0; }
+    return 0;
+}
+
 int pv_process_device(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, const pv_index_info *info,
                       const uint32_t *sc_idx, const uint32_t *sc_sec, void *stream)
 {
@@ -2714,6 +2828,10 @@ int pv_process_device(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, 
     }
     const uint64_t n = info->n_records;
     ensure_started(c, info->first_sec, info->first_nsec);
+    if (c->dhcp) {
+        // the DHCP handler's own pass over the batch (the Net and DNS passes below know nothing of it)
+        if (int rc = dhcp_stage(c, d_recs, d_offs, info, st)) return rc;
+    }
     std::vector<Shift> nsh, dsh;
     if (int rc = batch_shifts(c, d_recs, d_offs, info, sc_idx, sc_sec, st, nsh, dsh)) return rc;
     HP(3);
@@ -3096,6 +3214,8 @@ int pv_process_dnstap(pv_ctx *c, const uint8_t *buf, size_t bytes, uint32_t msg_
     std::lock_guard<std::mutex> g(c->mu);
     if (int rc = merged_refuse(c)) return rc;
     if (c->geo[0].on || c->geo[1].on) return c->fail(PV_EUNSUPPORTED, "geo databases: the dnstap input's geo metrics are not built");
+    // DhcpStreamHandler's constructor takes a pcap input only (DhcpStreamHandler.cpp:9-18)
+    if (c->dhcp) return c->fail(PV_EUNSUPPORTED, "DhcpStreamHandler: unsupported input event proxy dnstap (the DHCP handler is attached)");
     hipSetDevice(c->device);
     std::vector<pvi::DtMessage> msgs;
     uint32_t frames = 0;
@@ -3812,6 +3932,7 @@ int pv_set_end_tstamp(pv_ctx *c, int64_t sec, int64_t nsec)
     // end_tstamp_signal: the live bucket of each manager becomes read-only
     c->net.meta[c->net.slots.front()].set_read_only(sec, nsec);
     c->dns.meta[c->dns.slots.front()].set_read_only(sec, nsec);
+    if (c->dhcp) c->dhcp->set_end(sec, nsec);
     c->ended = true;
     return 0;
 }
@@ -3834,6 +3955,7 @@ int pv_check_period_shift(pv_ctx *c, int64_t sec, int64_t nsec)
         c->net.clean[c->net.slot_at(1)] = false;
         win_shift(c, c->net, sec, nsec);
     }
+    if (c->dhcp) c->dhcp->check_period_shift(sec, nsec);
     if (sec < c->dns.next_shift_sec) return 0;
     return dns_period_shift(c, sec, nsec);
 }

@@ -42,6 +42,7 @@
 #include "pv_ingest.h"
 #include "pv_geodb.h"
 #include "pv_layout.h"
+#include "pv_dhcp.h"
 
 // The kernel's name fingerprint (pv_parse.h NameStats + fp56), compiled for the host so
 // pv_set_dns_filters can key "only_qname" names exactly as the DNS pass keys first-query names.
@@ -171,6 +172,12 @@ extern "C" __global__ void pv_bpf_secs(const uint8_t *out, const uint32_t *ooffs
 extern "C" __global__ void pv_bpf_secs_compact(const uint32_t *flag, const uint32_t *pos, const uint32_t *sec, uint32_t nk, uint32_t cap,
                                                uint32_t *sci, uint32_t *scs);
 extern "C" hipError_t pv_exclusive_scan_u32(void *tmp, size_t *tmp_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s);
+// the DHCP handler's device stage (pv_dhcp.hip)
+extern "C" __global__ void pv_dhcp_scan(const uint8_t *recs, const uint32_t *offs, uint32_t n, uint32_t linktype, uint32_t ts_nano,
+                                        const PvParams *P, unsigned long long *mask, uint32_t *cnt);
+extern "C" __global__ void pv_dhcp_decode(const uint8_t *recs, const uint32_t *offs, uint32_t n, uint32_t linktype, uint32_t ts_nano,
+                                          const PvParams *P, const unsigned long long *mask, const uint32_t *rank, uint32_t base,
+                                          uint32_t cap, PvDhcpEvent *ev, uint8_t *arena, uint32_t arena_cap, uint32_t *arena_top);
 extern "C" __global__ void pv_topn_xcount(const PvParams *P, PvXTabs T, uint32_t *cnt);
 extern "C" __global__ void pv_topn_xscan(uint32_t reg_log2, uint32_t W, const uint32_t *cnt, uint32_t *off, uint32_t *hdr);
 extern "C" __global__ void pv_topn_xwrite(const PvParams *P, PvXTabs T, const uint32_t *off, ulonglong2 *out);
@@ -586,6 +593,24 @@ struct pv_ctx {
     // top-N pipeline, so while it counts, the passes log and combine those entries even with
     // top_ips disabled; the outputs follow net_groups and then show no top_ipv4 / top_ipv6.
     uint32_t dev_net_groups() const { return net_groups | (geo_counting() ? (uint32_t)PV_NET_TOP_IPS : 0u); }
+    // The DHCP handler (pv_set_dhcp; null = not attached): its host manager and the device stage's
+    // buffers, allocated once at attach time (no hipMalloc in a steady-state batch): per-tile
+    // masks, counts and rank bases for max_records, a round's events and hostname arena, a zeroed
+    // PvParams for parse_record, the scan's temporary storage
+    std::unique_ptr<pvdhcp::Manager> dhcp;
+    pv_dhcp_config dhcp_cfg{};
+    uint32_t dhcp_cap = 0; // events a round stores
+    unsigned long long *d_dh_mask = nullptr;
+    uint32_t *d_dh_cnt = nullptr, *d_dh_rank = nullptr, *d_dh_top = nullptr;
+    PvDhcpEvent *d_dh_ev = nullptr;
+    uint8_t *d_dh_arena = nullptr;
+    PvParams *d_dh_params = nullptr;
+    void *d_dh_scan = nullptr;
+    size_t dh_scan_bytes = 0;
+    std::vector<PvDhcpEvent> h_dh_ev;
+    std::vector<uint8_t> h_dh_arena;
+    double dhcp_scan_ms = 0; // stamped pv_dhcp_scan launches (pv_set_kernel_timing)
+    uint64_t dhcp_scan_launches = 0;
     std::vector<pv_bpf_insn> bpf; // the pcap input's BPF program (pv_set_bpf), empty = none
     // the program on the device and the filtered batch (pv_process_device runs the filter there)
     pv_bpf_insn *d_bpf = nullptr;

@@ -1211,6 +1211,30 @@ void dns2_metrics(pv_ctx *c, Sink &p, const HostBucket &b)
     p.add = base;
 }
 
+// DhcpMetricsBucket::to_prometheus (src/handlers/dhcp/DhcpStreamHandler.cpp:123-151); names and
+// descriptions from DhcpStreamHandler.h:65-89 (the rates write nothing)
+void dhcp_metrics(pv_ctx *c, Prom &p, const pvdhcp::Bucket &b)
+{
+    using namespace pvdhcp;
+    p.gauge("dhcp_wire_packets_events", "Total DHCP wire packets events", b.c[C_EVENTS]);
+    p.gauge("dhcp_wire_packets_deep_samples", "Total DHCP wire packets that were sampled for deep inspection", b.c[C_DEEP]);
+    p.gauge("dhcp_wire_packets_discover", "Total DHCP packets with message type DISCOVER", b.c[C_DISCOVER]);
+    p.gauge("dhcp_wire_packets_offer", "Total DHCP packets with message type OFFER", b.c[C_OFFER]);
+    p.gauge("dhcp_wire_packets_request", "Total DHCP packets with message type REQUEST", b.c[C_REQUEST]);
+    p.gauge("dhcp_wire_packets_ack", "Total DHCP packets with message type ACK", b.c[C_ACK]);
+    p.gauge("dhcp_wire_packets_solicit", "Total DHCPv6 packets with message type SOLICIT", b.c[C_SOLICIT]);
+    p.gauge("dhcp_wire_packets_advertise", "Total DHCPv6 packets with message type ADVERTISE", b.c[C_ADVERTISE]);
+    p.gauge("dhcp_wire_packets_request_v6", "Total DHCPv6 packets with message type REQUEST", b.c[C_REQUEST_V6]);
+    p.gauge("dhcp_wire_packets_reply", "Total DHCPv6 packets with message type REPLY", b.c[C_REPLY]);
+    p.gauge("dhcp_wire_packets_total", "Total DHCP/DHCPv6 wire packets matching the configured filter(s)", b.c[C_TOTAL]);
+    p.gauge("dhcp_wire_packets_filtered", "Total DHCP/DHCPv6 wire packets seen that did not match the configured filter(s) (if any)",
+            b.c[C_FILTERED]);
+    const size_t topn = c->cfg.topn_count;
+    const uint32_t pct = c->cfg.topn_percentile_threshold;
+    p.topn("dhcp_top_clients", "client", "Top DHCP clients", {b.clients.begin(), b.clients.end()}, topn, pct);
+    p.topn("dhcp_top_servers", "server", "Top DHCP servers", {b.servers.begin(), b.servers.end()}, topn, pct);
+}
+
 // KLL inclusive rank rule on exact data
 } // namespace pvh
 
@@ -1250,6 +1274,15 @@ int pv_window_json(pv_ctx *c, uint32_t period, int merged, char **out)
         if (c->dns2_groups) dns2_json(c, j, b);
         else dns_json(c, j, b);
         j.end_obj();
+    }
+    if (c->dhcp) {
+        // the DHCP handler's own window, rendered by its manager (pv_dhcp.cpp)
+        pvdhcp::Bucket b;
+        std::string err;
+        if (!c->dhcp->window(period, merged != 0, b, err)) return c->fail(PV_EINVAL, "%s", err.c_str());
+        j.key("dhcp");
+        j.sep();
+        j.s += pvdhcp::Manager::json(b, c->cfg.topn_count, c->cfg.topn_percentile_threshold);
     }
     j.end_obj();
     *out = strdup(j.s.c_str());
@@ -1341,6 +1374,7 @@ extern "C" {
 
 int pv_bucket_merge(pv_ctx *c, uint32_t handler, pv_bucket **bucket, uint32_t period, int prometheus, int merged)
 {
+    if (handler == PV_HANDLER_DHCP) return c->fail(PV_EUNSUPPORTED, "bucket merge: external buckets are not built for the DHCP handler");
     if (!bucket || (handler != PV_HANDLER_NET && handler != PV_HANDLER_DNS)) return c->fail(PV_EINVAL, "bucket merge: one handler");
     std::lock_guard<std::mutex> g(c->mu); // values drained under the lock (pv_window_json)
     int rc = sync_xvals(c);
@@ -1500,6 +1534,13 @@ int pv_window_prometheus(pv_ctx *c, uint32_t period, uint32_t handlers, const ch
         if (c->dns2_groups) dns2_metrics(c, p, b);
         else dns_metrics(c, p, b);
     }
+    if ((handlers & PV_HANDLER_DHCP) && c->dhcp) {
+        pvdhcp::Bucket b;
+        std::string err;
+        const uint32_t dper = period != PV_PERIOD_AUTO ? period : (c->dhcp->periods() > 1 ? 1u : 0u);
+        if (!c->dhcp->window(dper, false, b, err)) return c->fail(PV_EINVAL, "%s", err.c_str());
+        dhcp_metrics(c, p, b);
+    }
     *out = strdup(p.o.str().c_str());
     return 0;
 }
@@ -1509,6 +1550,7 @@ int pv_window_opentelemetry(pv_ctx *c, uint32_t period, uint32_t handlers, const
 {
     *out = nullptr;
     *bytes = 0;
+    if (handlers & PV_HANDLER_DHCP) return c->fail(PV_EUNSUPPORTED, "window_opentelemetry: not built for the DHCP handler");
     std::lock_guard<std::mutex> g(c->mu); // values drained under the lock (pv_window_json)
     int rc = sync_xvals(c);
     if (rc) return rc;

@@ -1,7 +1,8 @@
 // SPDX-License-Identifier: MPL-2.0
 // pvgpu-reader — GPU counterpart of cmd/pktvisor-reader/main.cpp:86-258 for the
-// net + dns handlers: pvgpu-reader [-H HOST_SPEC] [--periods N] FILE
-// Prints {"<N>m": {"packets": {...}, "dns": {...}}} like the reference.
+// net + dns handlers: pvgpu-reader [-H HOST_SPEC] [--periods N] [--dhcp] FILE
+// Prints {"<N>m": {"packets": {...}, "dns": {...}}} like the reference; --dhcp attaches the
+// DHCP handler too (pktvisor-reader's default) and adds its "dhcp" object.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,10 +17,12 @@ int main(int argc, char **argv)
 {
     std::string host, file;
     unsigned periods = 5;
+    bool dhcp = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a == "-H" && i + 1 < argc) host = argv[++i];
         else if (a == "--periods" && i + 1 < argc) periods = (unsigned)atoi(argv[++i]);
+        else if (a == "--dhcp") dhcp = true;
         else file = a;
     }
     std::ifstream f(file, std::ios::binary);
@@ -42,6 +45,10 @@ int main(int argc, char **argv)
     pv_ctx *ctx = nullptr;
     int rc = pv_create(&cfg, &ctx);
     if (rc) { fprintf(stderr, "Fatal error: %s\n", ctx ? pv_last_error(ctx) : "pv_create"); pv_destroy(ctx); return 1; }
+    if (dhcp) {
+        pv_dhcp_config dc{};
+        if (pv_set_dhcp(ctx, &dc)) { fprintf(stderr, "Fatal error: %s\n", pv_last_error(ctx)); pv_destroy(ctx); return 1; }
+    }
     rc = pv_process_host(ctx, buf.data() + 24, buf.size() - 24);
     if (!rc && nrec) {
         // end_tstamp_signal with the last record (PcapInputStream.cpp:514-517)
