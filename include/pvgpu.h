@@ -609,6 +609,16 @@ int pv_set_kernel_timing(pv_ctx *ctx, uint32_t every);
  * name rocprofv3 reports for the launches pv_kernel_timing times. */
 const char *pv_net_kernel_name(pv_ctx *ctx);
 int pv_kernel_timing(pv_ctx *ctx, double *total_ms, uint64_t *launches, int reset);
+/* Which launch chain the one-span batches took since the last reset (diagnostics). A lean batch
+ * that follows one without a UDP DNS message and without a deferred (VLAN, IPv6, option-carrying)
+ * record starts on the short chain: the Net pass, the top-N combine and merge, with no
+ * pv_net_slow_list, DNS pass or names launch. The guess cannot change a result: the combine
+ * leaves a batch that needs either pass untouched and the regular chain then runs on it.
+ * out[0] batches started on the short chain, out[1] those of them that fell back to the regular
+ * chain, out[2] names kernels launched late on the short chain, out[3] batches on the regular
+ * chain. Contexts with Net v2 or GeoIP counting never start the short chain; PV_PLAIN_CHAIN=0 in
+ * the environment (read at every batch) keeps every batch on the regular one. */
+int pv_chain_stats(pv_ctx *ctx, uint64_t out[4], int reset);
 
 /* ---- GeoIP / ASN databases (MaxMind DB 2.0), the reference's MaxmindDB (src/GeoDB.h:27-41,
  * src/GeoDB.cpp). A database is parsed from untrusted bytes and compiled at open time: every data

@@ -2303,6 +2303,20 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     }
     // PV_NET_KERNEL=span: the span-load pass (top-IPs groups), kept for A/B runs
     const bool span = lean && tc && force && !strcmp(force, "span");
+    // The short chain: on the same guess as the combine's fan (the last batch was a lean pass
+    // without DNS messages or deferred records), a lean batch launches only the Net pass, the
+    // combine and the merge: pv_net_slow_list, the DNS pass and the names kernel would each return
+    // at their first line. The guess cannot change a result: the combine reads the Net pass's two
+    // counts and leaves a batch that has either untouched, and the regular chain then runs from
+    // pv_net_slow_list on (below, after the read-back). Not with Net v2 (its pass sits between), nor
+    // with geo counting (pv_geo_count reads the combine's lists). PV_PLAIN_CHAIN=0 keeps every
+    // batch on the regular chain.
+    bool plain = lean && !(force && !strcmp(force, "span")) && c->cb_plain && !c->net2_groups && !c->geo_counting();
+    if (plain) {
+        const char *pc = getenv("PV_PLAIN_CHAIN");
+        if (pc && atoi(pc) == 0) plain = false;
+    }
+    P.plain_chain = plain ? 1u : 0u;
     // both lean passes defer general-path records to pv_net_slow_list
     if (lean) {
         if (c->slow_cap < P.n) {
@@ -2359,67 +2373,110 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     }
     if (general) hipExtLaunchKernelGGL(pv_net_kernel, dim3(grid), dim3(PV_NET_THREADS), 0, st, e0, e1, 0, dp);
     else if (lean) {
-        // the lean pass, then its deferred general-path records (the dispatch stamps span both)
-        if (span) hipExtLaunchKernelGGL(pv_net_kernel_span, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, (hipEvent_t) nullptr, 0, dp);
-        else if (tc) hipExtLaunchKernelGGL(pv_net_kernel_reg_tc, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, (hipEvent_t) nullptr, 0, dp);
-        else hipExtLaunchKernelGGL(pv_net_kernel_reg, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, (hipEvent_t) nullptr, 0, dp);
-        hipExtLaunchKernelGGL(pv_net_slow_list, dim3(c->cus * 2), dim3(256), 0, st, (hipEvent_t) nullptr, e1, 0, dp);
+        // the lean pass, then its deferred general-path records (the dispatch stamps span both; on
+        // the short chain, which has no second launch, both stamps are the lean pass's)
+        hipEvent_t l1 = plain ? e1 : (hipEvent_t) nullptr;
+        if (span) hipExtLaunchKernelGGL(pv_net_kernel_span, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, l1, 0, dp);
+        else if (tc) hipExtLaunchKernelGGL(pv_net_kernel_reg_tc, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, l1, 0, dp);
+        else hipExtLaunchKernelGGL(pv_net_kernel_reg, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, l1, 0, dp);
+        if (!plain) hipExtLaunchKernelGGL(pv_net_slow_list, dim3(c->cus * 2), dim3(256), 0, st, (hipEvent_t) nullptr, e1, 0, dp);
     }
     else hipExtLaunchKernelGGL(pv_net_kernel_ns, dim3(grid), dim3(PV_NET_THREADS), 0, st, e0, e1, 0, dp);
     e = hipGetLastError();
     if (e != hipSuccess) return c->hipfail(e, "launch pv_net_kernel");
-    if (P.f_flags & (PVDF_ONLY_QSUFFIX | PVDF_PSL))
-        hipLaunchKernelGGL(pv_dns_suffix, dim3(grid), dim3(256), 0, st, (const PvParams *)c->d_params);
-    // the DNS pass walks the logical grid's ranges with its resident grid
-    const uint32_t dns_grid = std::min<uint32_t>(grid, (uint32_t)(c->cus * c->dns_wg_per_cu));
-    if (P.f_flags & (PVDF_ONLY_QSUFFIX | PVDF_PSL))
-        hipLaunchKernelGGL(pv_dns_kernel_sfx, dim3(dns_grid), dim3(64 * PV_DNS_WAVES), 0, st, (const PvParams *)c->d_params);
-    else if (P.f_flags)
-        hipLaunchKernelGGL(pv_dns_kernel_f, dim3(dns_grid), dim3(64 * PV_DNS_WAVES), 0, st, (const PvParams *)c->d_params);
-    else
-        hipLaunchKernelGGL(pv_dns_kernel, dim3(dns_grid), dim3(64 * PV_DNS_WAVES), 0, st, (const PvParams *)c->d_params);
-    if (c->dns_groups & PV_DNS_TOP_ECS)
-        hipLaunchKernelGGL(pv_dns_ecs, dim3((uint32_t)c->cus * 2), dim3(256), 0, st, (const PvParams *)c->d_params);
-    if (c->net2_groups) hipLaunchKernelGGL(pv_net2_kernel, dim3(grid), dim3(256), 0, st, (const PvParams *)c->d_params);
-    // top-N: combine each workgroup's updates into a list sorted by table region, merge
-    // each region's runs in LDS, decode the names of new entries
-    static int cb_threads = 0; // the kernel's own launch bound (tuning builds change it)
+    static int cb_threads = 0; // the combine kernel's own launch bound (tuning builds change it)
     if (!cb_threads) {
         hipFuncAttributes fa{};
         cb_threads = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(pv_topn_combine)) == hipSuccess ? fa.maxThreadsPerBlock
                                                                                                              : PV_CB_THREADS;
     }
-    hipLaunchKernelGGL(c->reg_log2 <= 10 ? pv_topn_combine : pv_topn_combine_r12, dim3(P.cb_grid), dim3(cb_threads), 0, st,
-                       (const PvParams *)c->d_params);
-    if (c->geo_counting()) {
-        // top_geo: one walk per combined IP entry (pv_geo_count reads the combine lists; the merge does not change them)
-        PvGeoArgs G{};
-        for (int k = 0; k < 2; k++) {
-            const pv_ctx::GeoAttach &g = c->geo[k];
-            if (!g.on) continue;
-            G.tree[k] = g.d_tree;
-            G.cnt[k] = g.d_cnt;
-            G.node_count[k] = g.node_count;
-            G.start4[k] = g.start4;
-            G.ip_version[k] = g.ip_version;
-            G.entries[k] = (uint32_t)g.dict.size();
+    const bool sfx = (P.f_flags & (PVDF_ONLY_QSUFFIX | PVDF_PSL)) != 0;
+    // the DNS stage: the suffix sizes, the DNS pass, its top_ecs updates, Net v2
+    auto dns_stage = [&]() {
+        if (sfx) hipLaunchKernelGGL(pv_dns_suffix, dim3(grid), dim3(256), 0, st, (const PvParams *)c->d_params);
+        // the DNS pass walks the logical grid's ranges with its resident grid
+        const uint32_t dns_grid = std::min<uint32_t>(grid, (uint32_t)(c->cus * c->dns_wg_per_cu));
+        if (sfx)
+            hipLaunchKernelGGL(pv_dns_kernel_sfx, dim3(dns_grid), dim3(64 * PV_DNS_WAVES), 0, st, (const PvParams *)c->d_params);
+        else if (P.f_flags)
+            hipLaunchKernelGGL(pv_dns_kernel_f, dim3(dns_grid), dim3(64 * PV_DNS_WAVES), 0, st, (const PvParams *)c->d_params);
+        else
+            hipLaunchKernelGGL(pv_dns_kernel, dim3(dns_grid), dim3(64 * PV_DNS_WAVES), 0, st, (const PvParams *)c->d_params);
+        if (c->dns_groups & PV_DNS_TOP_ECS)
+            hipLaunchKernelGGL(pv_dns_ecs, dim3((uint32_t)c->cus * 2), dim3(256), 0, st, (const PvParams *)c->d_params);
+        if (c->net2_groups) hipLaunchKernelGGL(pv_net2_kernel, dim3(grid), dim3(256), 0, st, (const PvParams *)c->d_params);
+    };
+    // top-N: combine each workgroup's updates into a list sorted by table region, merge
+    // each region's runs in LDS
+    auto topn_stage = [&]() {
+        hipLaunchKernelGGL(c->reg_log2 <= 10 ? pv_topn_combine : pv_topn_combine_r12, dim3(P.cb_grid), dim3(cb_threads), 0, st,
+                           (const PvParams *)c->d_params);
+        if (c->geo_counting()) {
+            // top_geo: one walk per combined IP entry (pv_geo_count reads the combine lists; the merge does not change them)
+            PvGeoArgs G{};
+            for (int k = 0; k < 2; k++) {
+                const pv_ctx::GeoAttach &g = c->geo[k];
+                if (!g.on) continue;
+                G.tree[k] = g.d_tree;
+                G.cnt[k] = g.d_cnt;
+                G.node_count[k] = g.node_count;
+                G.start4[k] = g.start4;
+                G.ip_version[k] = g.ip_version;
+                G.entries[k] = (uint32_t)g.dict.size();
+            }
+            hipLaunchKernelGGL(pv_geo_count, dim3(std::min<uint32_t>(P.cb_grid, (uint32_t)c->cus * 8)), dim3(256), 0, st,
+                               (const PvParams *)c->d_params, G);
         }
-        hipLaunchKernelGGL(pv_geo_count, dim3(std::min<uint32_t>(P.cb_grid, (uint32_t)c->cus * 8)), dim3(256), 0, st,
-                           (const PvParams *)c->d_params, G);
+        hipLaunchKernelGGL(pv_topn_merge, dim3(2u << c->reg_log2), dim3(pv_topn_merge_threads()), 0, st, (const PvParams *)c->d_params);
+    };
+    // decode the names of new entries: as many workgroups as are resident (LDS: two per CU), each
+    // pipelining its entries
+    auto names_stage = [&]() {
+        hipLaunchKernelGGL(sfx ? pv_topn_names_sfx : pv_topn_names, dim3((uint32_t)c->cus * 2), dim3(256), 0, st,
+                           (const PvParams *)c->d_params);
+    };
+    uint32_t status[ST_WORDS];
+    // the status words, the tables' live counts and the overflow words, read behind the chain
+    auto read_status = [&]() -> hipError_t {
+        hipError_t r = hipGetLastError();
+        if (r != hipSuccess) return r;
+        if ((r = hipMemcpyAsync(c->h_status, c->d_status, ST_RB_WORDS * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return r;
+        if ((r = hipStreamSynchronize(st)) != hipSuccess) return r;
+        memcpy(status, c->h_status, sizeof status);
+        return hipSuccess;
+    };
+    if (!plain) {
+        dns_stage();
+        topn_stage();
+        names_stage();
+        c->chain_n[3]++;
+    } else {
+        topn_stage();
+        c->chain_n[0]++;
     }
-    hipLaunchKernelGGL(pv_topn_merge, dim3(2u << c->reg_log2), dim3(pv_topn_merge_threads()), 0, st, (const PvParams *)c->d_params);
-    // names: as many workgroups as are resident (LDS: two per CU), each pipelining its entries
-    hipLaunchKernelGGL((P.f_flags & (PVDF_ONLY_QSUFFIX | PVDF_PSL)) ? pv_topn_names_sfx : pv_topn_names, dim3((uint32_t)c->cus * 2),
-                       dim3(256), 0, st, (const PvParams *)c->d_params);
-    if (!hip_ok(e = hipGetLastError())) return c->hipfail(e, "launch");
 
     // ---- transactions: pair responses with queries (sort by key, then record index)
-    uint32_t status[ST_WORDS];
     HP(14);
-    if (!hip_ok(e = hipMemcpyAsync(c->h_status, c->d_status, ST_RB_WORDS * 4, hipMemcpyDeviceToHost, st)) ||
-        !hip_ok(e = hipStreamSynchronize(st)))
-        return c->hipfail(e, "kernel execution");
-    memcpy(status, c->h_status, sizeof status);
+    if (!hip_ok(e = read_status())) return c->hipfail(e, "kernel execution");
+    if (plain && (status[ST_NDNS] || status[ST_NSLOW])) {
+        // the guess was wrong: the combine left the batch untouched (and the merge had no handler
+        // to work for), so the regular chain runs on the Net pass's results as they stand
+        c->chain_n[1]++;
+        P.plain_chain = 0;
+        c->h_params->plain_chain = 0;
+        if (!hip_ok(e = upload_params(c->d_params, c->h_params, sizeof P, st))) return c->hipfail(e, "parameter upload");
+        hipLaunchKernelGGL(pv_net_slow_list, dim3(c->cus * 2), dim3(256), 0, st, dp);
+        dns_stage();
+        topn_stage();
+        names_stage();
+        if (!hip_ok(e = read_status())) return c->hipfail(e, "kernel execution");
+    } else if (plain && status[ST_NNEW]) {
+        // created named entries without a deferred record: their names, before anything reads or
+        // purges the tables
+        c->chain_n[2]++;
+        names_stage();
+        if (!hip_ok(e = read_status())) return c->hipfail(e, "kernel execution");
+    }
     c->dns_heavy = (uint64_t)status[ST_NDNS] * 2 > n;
     c->cb_plain = lean && status[ST_NDNS] == 0 && status[ST_NSLOW] == 0;
     if (status[ST_FLAGS] & PVF_NAMES_PENDING) {
@@ -2786,6 +2843,16 @@ extern "C" int pv_dhcp_timing(pv_ctx *c, double *scan_ms, uint64_t *launches, in
     if (scan_ms) *scan_ms = c->dhcp_scan_ms;
     if (launches) *launches = c->dhcp_scan_launches;
     if (reset) { c->dhcp_scan_ms = 0; c->dhcp_scan_launches = 0; }
+    return 0;
+}
+
+extern "C" int pv_chain_stats(pv_ctx *c, uint64_t out[4], int reset)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int k = 0; k < 4; k++) {
+        if (out) out[k] = c->chain_n[k];
+        if (reset) c->chain_n[k] = 0;
+    }
     return 0;
 }
 

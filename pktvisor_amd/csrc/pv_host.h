@@ -671,6 +671,9 @@ struct pv_ctx {
     int reg_wg_per_cu = 1; // workgroups per CU of the register-window Net pass
     uint32_t cb_fan = 1;   // grid ranges per top-N combine workgroup (batches the compact table does not suit)
     bool cb_plain = false; // the last batch was a lean pass without DNS messages or deferred records
+    // pv_chain_stats: batches started on the short chain, those that fell back to the regular
+    // one, late names launches, batches on the regular chain
+    uint64_t chain_n[4] = {0, 0, 0, 0};
     int dns_wg_per_cu = 1; // resident workgroups per CU of the DNS pass (its register count)
     const char *net_kernel = "none"; // the Net-pass kernel the last span launched (pv_net_kernel_name)
     uint64_t *d_dq = nullptr; // DNS work lists (32-B messages)

@@ -3325,6 +3325,11 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
 {
     using St = CombState<CN, NR>;
     __shared__ St S;
+    // the short chain (no DNS pass, no pv_net_slow_list ahead of this kernel): a batch the Net pass
+    // found a DNS message or a deferred record in is left as it is for the regular chain, which the
+    // host runs next: no list, no run word, no cb_hm word, no tp_hands bit (pv_topn_merge then
+    // returns at its first line)
+    if (P.plain_chain && (*P.n_dns | *P.n_slow)) return;
     TST_DECL
     const uint32_t nreg = 2u << P.reg_log2; // run keys
     // this workgroup's grid ranges [g0, g1) (cb_fan of them): their update logs and IP logs into

@@ -468,6 +468,9 @@ struct PvParams {
                           // set the count words' PV_CNT_SEEN_* flags (0: it does neither)
     uint32_t dbg; // profiling knob (PV_DEBUG_STAGES env): 1 stop after staging, 2 after parse, 4 no DNS lane,
                   // 16 no DNS name decode, 32 no DNS table updates
+    uint32_t plain_chain; // the short chain (the host guessed a batch without DNS messages or deferred records
+                          // and launched neither pass): pv_topn_combine returns untouched when *n_dns or
+                          // *n_slow says otherwise, and the host then runs the regular chain
     PV_G uint32_t *flags;
     // DNS v1 filters (DnsStreamHandler::_filtering, dns/v1/DnsStreamHandler.cpp:538-648)
     uint32_t f_flags, f_rcode_mask, f_ancount, f_nq;
