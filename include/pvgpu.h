@@ -619,6 +619,12 @@ int pv_kernel_timing(pv_ctx *ctx, double *total_ms, uint64_t *launches, int rese
  * chain. Contexts with Net v2 or GeoIP counting never start the short chain; PV_PLAIN_CHAIN=0 in
  * the environment (read at every batch) keeps every batch on the regular one. */
 int pv_chain_stats(pv_ctx *ctx, uint64_t out[4], int reset);
+/* Short-chain batches whose Net pass and top-N combine ran as one launch (pv_net_combine_plain:
+ * the default groups' lean pass, three compact ranges a combine workgroup, one workgroup a CU, not
+ * a dispatch-stamped batch) since the last reset: out[0] such batches, out[1] those of them that
+ * fell back to the regular chain. A choice of speed only; PV_FUSE_PLAIN=0 in the environment
+ * (read at every batch) keeps the two launches. */
+int pv_fuse_stats(pv_ctx *ctx, uint64_t out[2], int reset);
 
 /* ---- GeoIP / ASN databases (MaxMind DB 2.0), the reference's MaxmindDB (src/GeoDB.h:27-41,
  * src/GeoDB.cpp). A database is parsed from untrusted bytes and compiled at open time: every data

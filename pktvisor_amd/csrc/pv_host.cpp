@@ -2317,6 +2317,22 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         if (pc && atoi(pc) == 0) plain = false;
     }
     P.plain_chain = plain ? 1u : 0u;
+    // The short chain's Net pass and combine as one launch (pv_net_combine_plain): the default
+    // groups' lean pass, groups of more than one range (the host's own pick: compact ones), and as
+    // many combine workgroups as the lean pass would launch, so workgroup b of either walks ranges
+    // [b * fan, (b + 1) * fan). PV_FUSE_PLAIN=0 keeps the two launches. (A dispatch-stamped batch
+    // keeps them too: below. The fan is above one only as the compact pick or as PV_CB_FAN; with
+    // PV_CB_COMPACT=0 beside a forced fan the fused workgroups run the generic table, for tests.)
+    bool fuse = plain && tc && P.cb_fan > 1 && P.cb_grid == reg_grid && c->reg_log2 <= 10;
+    if (fuse) {
+        const char *fp = getenv("PV_FUSE_PLAIN");
+        if (fp && atoi(fp) == 0) fuse = false;
+    }
+    {
+        // -DPV_RANGE_AB builds: the lean pass alone with the fused kernel's range mapping
+        const char *nc = getenv("PV_NET_CONTIG");
+        P.net_contig = nc && atoi(nc) != 0 && lean && P.cb_fan > 1 && P.cb_grid == reg_grid ? 1u : 0u;
+    }
     // both lean passes defer general-path records to pv_net_slow_list
     if (lean) {
         if (c->slow_cap < P.n) {
@@ -2355,6 +2371,8 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     // asks for are stamped)
     const bool timed = c->timing_every && (c->timing_ctr++ % c->timing_every) == 0;
     hipEvent_t e0 = timed ? c->ev_start : nullptr, e1 = timed ? c->ev_stop : nullptr;
+    // (the stamps bracket the Net pass alone: a stamped batch is not fused)
+    if (timed) fuse = false;
     if (P.gfilt) {
         // the geo filters' verdict of every record of the span, for the general pass to read
         PvGeoArgs G{};
@@ -2376,7 +2394,8 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         // the lean pass, then its deferred general-path records (the dispatch stamps span both; on
         // the short chain, which has no second launch, both stamps are the lean pass's)
         hipEvent_t l1 = plain ? e1 : (hipEvent_t) nullptr;
-        if (span) hipExtLaunchKernelGGL(pv_net_kernel_span, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, l1, 0, dp);
+        if (fuse) hipLaunchKernelGGL(pv_net_combine_plain, dim3(P.cb_grid), dim3(PV_CB_THREADS), 0, st, dp);
+        else if (span) hipExtLaunchKernelGGL(pv_net_kernel_span, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, l1, 0, dp);
         else if (tc) hipExtLaunchKernelGGL(pv_net_kernel_reg_tc, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, l1, 0, dp);
         else hipExtLaunchKernelGGL(pv_net_kernel_reg, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, l1, 0, dp);
         if (!plain) hipExtLaunchKernelGGL(pv_net_slow_list, dim3(c->cus * 2), dim3(256), 0, st, (hipEvent_t) nullptr, e1, 0, dp);
@@ -2408,9 +2427,10 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     };
     // top-N: combine each workgroup's updates into a list sorted by table region, merge
     // each region's runs in LDS
-    auto topn_stage = [&]() {
-        hipLaunchKernelGGL(c->reg_log2 <= 10 ? pv_topn_combine : pv_topn_combine_r12, dim3(P.cb_grid), dim3(cb_threads), 0, st,
-                           (const PvParams *)c->d_params);
+    auto topn_stage = [&](bool combined = false) {
+        if (!combined)
+            hipLaunchKernelGGL(c->reg_log2 <= 10 ? pv_topn_combine : pv_topn_combine_r12, dim3(P.cb_grid), dim3(cb_threads), 0, st,
+                               (const PvParams *)c->d_params);
         if (c->geo_counting()) {
             // top_geo: one walk per combined IP entry (pv_geo_count reads the combine lists; the merge does not change them)
             PvGeoArgs G{};
@@ -2451,17 +2471,23 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         names_stage();
         c->chain_n[3]++;
     } else {
-        topn_stage();
+        topn_stage(fuse);
         c->chain_n[0]++;
+        if (fuse) c->fuse_n[0]++;
     }
 
     // ---- transactions: pair responses with queries (sort by key, then record index)
     HP(14);
     if (!hip_ok(e = read_status())) return c->hipfail(e, "kernel execution");
     if (plain && (status[ST_NDNS] || status[ST_NSLOW])) {
-        // the guess was wrong: the combine left the batch untouched (and the merge had no handler
-        // to work for), so the regular chain runs on the Net pass's results as they stand
+        // the guess was wrong: the combine left the batch untouched and the merge returned at its
+        // first line, so the regular chain runs on the Net pass's results as they stand. (Fused:
+        // workgroups whose own ranges were plain have listed them. The chain's combine runs over
+        // every workgroup with the same fan and the same logs plus the deferred records' entries:
+        // it writes every cb_hm and cb_cnt word and every list again, the run words of each handler a
+        // workgroup has entries of, a superset of the fused one's, and sets the tp_hands bits again.)
         c->chain_n[1]++;
+        if (fuse) c->fuse_n[1]++;
         P.plain_chain = 0;
         c->h_params->plain_chain = 0;
         if (!hip_ok(e = upload_params(c->d_params, c->h_params, sizeof P, st))) return c->hipfail(e, "parameter upload");
@@ -2540,6 +2566,28 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
                     ms[0] / std::max<uint64_t>(nm, 1), ms[1] / std::max<uint64_t>(nm, 1), ms[2] / std::max<uint64_t>(nm, 1),
                     ms[3] / std::max<uint64_t>(nm, 1), ms[4] / std::max<uint64_t>(nm, 1));
             hipMemset(c->d_stamps + (1u << 20), 0, tv.size() * 8);
+        }
+        // the lean Net workgroups' wall-clock ticks (start, Net end; fused: hand-over, kernel end),
+        // relative to the first start
+        std::vector<uint64_t> nv((size_t)reg_grid * 4);
+        int khz = 0;
+        hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device);
+        if (lean && hip_ok(hipMemcpy(nv.data(), c->d_stamps + (1u << 20) + (1u << 18), nv.size() * 8, hipMemcpyDeviceToHost)) && nv[0]) {
+            uint64_t first = ~0ull;
+            for (uint32_t w = 0; w < reg_grid; w++) first = std::min(first, nv[w * 4]);
+            const double us = khz > 0 ? 1000.0 / khz : 0.01;
+            fprintf(stderr, "pv_tstamps net (%u wg, %s):", reg_grid, fuse ? "fused" : "pair");
+            static const char *nm[4] = {"start", "net_end", "handover", "end"};
+            for (int k = 0; k < (fuse ? 4 : 2); k++) {
+                std::vector<double> v;
+                for (uint32_t w = 0; w < reg_grid; w++)
+                    if (nv[w * 4 + k]) v.push_back((double)(nv[w * 4 + k] - first) * us);
+                if (v.empty()) continue;
+                std::sort(v.begin(), v.end());
+                fprintf(stderr, " %s min=%.2f med=%.2f max=%.2f us", nm[k], v.front(), v[v.size() / 2], v.back());
+            }
+            fprintf(stderr, "\n");
+            hipMemset(c->d_stamps + (1u << 20) + (1u << 18), 0, nv.size() * 8);
         }
     }
     if (getenv("PV_STAMPS")) {
@@ -2843,6 +2891,16 @@ extern "C" int pv_dhcp_timing(pv_ctx *c, double *scan_ms, uint64_t *launches, in
     if (scan_ms) *scan_ms = c->dhcp_scan_ms;
     if (launches) *launches = c->dhcp_scan_launches;
     if (reset) { c->dhcp_scan_ms = 0; c->dhcp_scan_launches = 0; }
+    return 0;
+}
+
+extern "C" int pv_fuse_stats(pv_ctx *c, uint64_t out[2], int reset)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int k = 0; k < 2; k++) {
+        if (out) out[k] = c->fuse_n[k];
+        if (reset) c->fuse_n[k] = 0;
+    }
     return 0;
 }
 

@@ -2124,13 +2124,30 @@ __device__ __forceinline__ void win_words(const uint4 (&W)[5], uint32_t sh, RecW
 // them as younger ops instead of waiting for them: a store takes microseconds to complete under
 // the read stream, and a wait that covers the previous tile's stores (as the branchy form's
 // does) stalls every tile on them (tools/ring_probe.hip: 138 -> 177 us on C2 with a 4-B store).
-template <uint32_t NW, bool TC = false>
+// FUSE: the Net phase of pv_net_combine_plain, run by the first NW waves of a larger workgroup
+// (the others execute this function's barriers beside it: the init's, two a range, the last): the
+// workgroup walks the ranges of its own combine group, [blockIdx.x * cb_fan, + cb_fan).
+#ifdef PV_TSTAMPS
+// diagnostic build: a Net workgroup's first and last wall-clock tick (and, fused, the hand-over's
+// and the kernel's last), at stamps[PV_TST_NET + 4 * workgroup ...]
+#define PV_TST_NET ((1u << 20) + (1u << 18))
+#define TST_WALL(P, k) if (threadIdx.x == 0) (P).stamps[PV_TST_NET + 4ull * blockIdx.x + (k)] = wall_clock64();
+#else
+#define TST_WALL(P, k)
+#endif
+__device__ __forceinline__ void net_ranges(PV_CREF(PvParams) P, bool contig, uint32_t &lb0, uint32_t &lb1, uint32_t &step)
+{
+    lb0 = blockIdx.x; lb1 = P.grid_main; step = gridDim.x;
+    if (contig) { lb0 = min(blockIdx.x * P.cb_fan, P.grid_main); lb1 = min(lb0 + P.cb_fan, P.grid_main); step = 1; }
+}
+template <uint32_t NW, bool TC = false, bool FUSE = false>
 __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
 {
     PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
     __shared__ NetRegState S;
+    TST_WALL(P, 0)
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    for (uint32_t b = threadIdx.x; b < PV_HBINS; b += blockDim.x) S.hist[b] = 0;
+    for (uint32_t b = threadIdx.x; b < PV_HBINS; b += (FUSE ? 64u * NW : blockDim.x)) S.hist[b] = 0;
     if (threadIdx.x == 0) { S.nd = 0; S.nx = 0; S.ns = 0; }
     if (threadIdx.x < PV_MAX_SHIFTS) S.dord[threadIdx.x] = P.dpos[threadIdx.x];
     __syncthreads();
@@ -2156,7 +2173,14 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
     // each workgroup walks the ranges of several grid workgroups (lb = blockIdx.x, + gridDim.x,
     // ...): the DNS pass, combine and merge keep the grid's partition, while the Net pass runs
     // one workgroup per CU (fewer, longer streams measured faster: tools/gpu_reg2.sh)
-    for (uint32_t lb = blockIdx.x; lb < P.grid_main; lb += gridDim.x) {
+#ifdef PV_RANGE_AB
+    uint32_t lb0, lb1, lbstep;
+    net_ranges(P, FUSE || P.net_contig, lb0, lb1, lbstep);
+    for (uint32_t lb = lb0; lb < lb1; lb += lbstep) {
+#else
+    for (uint32_t lb = FUSE ? blockIdx.x * P.cb_fan : blockIdx.x; lb < (FUSE ? min(blockIdx.x * P.cb_fan + P.cb_fan, P.grid_main) : P.grid_main);
+         lb += FUSE ? 1u : gridDim.x) {
+#endif
     const uint64_t wbeg = (uint64_t)lb * P.wt_per_block;
     const uint64_t wend = min<uint64_t>(wbeg + P.wt_per_block, nwt);
     const uint32_t ntl = wend > wbeg + wave ? (uint32_t)((wend - wbeg - wave + NW - 1) / NW) : 0u;
@@ -2309,7 +2333,9 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
     }
     // this range's DNS list: its count, and the slot counter reset for the next range (LDS-only
     // barriers: the range's IP-log and DNS-list stores are other kernels' to read, and waiting
-    // for them here would stall every wave on their completion)
+    // for them here would stall every wave on their completion; FUSE: the waves beside the Net
+    // phase read the range's IP log after these barriers, so there the wait is taken)
+    if constexpr (FUSE) __builtin_amdgcn_s_waitcnt(PV_WAIT_VMCNT0);
     lds_barrier();
     if (threadIdx.x == 0) {
         P.mq_cnt[lb] = 0;
@@ -2336,8 +2362,9 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
     K.sum = P.sum; K.net_groups = groups; K.net_filter_all = 0; K.gfilt = nullptr;
     if (any) knet_flush(K, slot, c);
     lds_barrier();
-    for (uint32_t b = threadIdx.x; b < PV_HBINS; b += blockDim.x)
+    for (uint32_t b = threadIdx.x; b < PV_HBINS; b += (FUSE ? 64u * NW : blockDim.x))
         if (S.hist[b]) ksum_add(K, slot, PV_OFF_PAYLOAD + b, S.hist[b]);
+    TST_WALL(P, 1)
 }
 
 // ------------------------------------------------------------------ the lean Net pass, span loads
@@ -3320,21 +3347,134 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, 
     return base + incl - v;
 }
 
-template <uint32_t CN, uint32_t NR>
-__device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
+// a word another wave of this workgroup stored earlier in the same kernel (FUSE: the Net phase's
+// logs and counts), read past the CU's vector cache: a relaxed agent-scope load (sc1). The writer
+// waited for its stores (vmcnt(0)) before the barrier this read follows (a range's first, or the
+// hand-over's), so the word is in this CU's own L2; no release fence and no flag, since no other
+// workgroup reads it before the kernel's end.
+template <bool FUSE, class T>
+__device__ __forceinline__ T ld_own(const PV_G T *p)
+{
+    if constexpr (FUSE) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else return *p;
+}
+// topn_combine's init by other threads than its own (tid of nt): the table, region counters and
+// table words cleared
+template <uint32_t CN, class St>
+__device__ __forceinline__ void comb_init(St &S, uint32_t nreg, uint32_t tid, uint32_t nt)
+{
+    for (uint32_t j = tid; j < CN; j += nt) { S.key[j] = 0; S.cnt[j] = 0; S.rep[j] = 0xffffffffu; }
+    for (uint32_t r = tid; r < nreg; r += nt) {
+        S.h[r] = 0;
+        if (!(r & 1)) S.tb[r >> 1] = 0;
+    }
+    if (tid == 0) S.nsp = 0;
+}
+// topn_combine's compact insert of one range (its loop body, for threads tid of bd): the fused
+// kernel's waves beside the Net phase insert a range while the Net waves stream the next one
+template <uint32_t CN, class St>
+__device__ __forceinline__ void comb_crange_own(PV_CREF(PvParams) P, St &S, PV_G ulonglong2 *sp, uint32_t gr, uint32_t cbase,
+                                                uint32_t tid, uint32_t bd)
+{
+    const PV_G uint32_t *ip4 = P.iplog32;
+    uint64_t a, z;
+    wg_records(P, gr, a, z);
+    const uint32_t nn = (uint32_t)(z - a), ra = (uint32_t)(a - cbase);
+    for (uint32_t j0 = tid; j0 < nn; j0 += PV_CB_U * bd) {
+        uint32_t ipv[PV_CB_U];
+        uint64_t dw[PV_CB_U];
+#pragma unroll
+        for (int u = 0; u < PV_CB_U; u++) {
+            const uint32_t j = j0 + u * bd;
+            ipv[u] = j < nn ? ld_own<true>(ip4 + a + j) : 0u;
+            dw[u] = j < nn ? ld_own<true>(P.ipdir + ((a + j) >> 6)) : 0ull;
+        }
+        uint32_t dir[PV_CB_U], pos[PV_CB_U], cur[PV_CB_U], rp[PV_CB_U];
+#pragma unroll
+        for (int u = 0; u < PV_CB_U; u++) {
+            const uint64_t r = a + j0 + (uint64_t)u * bd;
+            dir[u] = (uint32_t)(dw[u] >> (r & 63)) & 1u;
+            pos[u] = comb_cpos<2 * CN>(ipv[u], dir[u]);
+            cur[u] = ipv[u] ? S.ckey[pos[u]] : 0u;
+            rp[u] = ipv[u] ? (S.crep[pos[u] >> 1] >> (16u * (pos[u] & 1u))) & 0xffffu : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < PV_CB_U; u++)
+            if (ipv[u]) comb_cadd_pre<2 * CN>(P, S, sp, ipv[u], dir[u], cbase, ra + j0 + u * bd, pos[u], cur[u], rp[u]);
+    }
+}
+// FUSE (pv_net_combine_plain, Pp set): the lean Net pass over this workgroup's own ranges runs
+// first, in waves 0-3, while the other waves clear the table, insert each range but the last as
+// the Net waves finish it, and park at the Net phase's barriers in between; the rest of the combine
+// starts on this CU as soon as its own ranges are logged. (The hand-over alone, with the whole
+// combine behind the last range, gained nothing: the slowest CU's Net phase is no shorter and its
+// whole combine still followed it. -DPV_FUSE_NO_EARLY builds that form; profiles/r10/fused_plain.)
+template <uint32_t CN, uint32_t NR, bool FUSE = false>
+__device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams *__restrict__ Pp = nullptr)
 {
     using St = CombState<CN, NR>;
     __shared__ St S;
+    constexpr uint32_t CK = 16; // compact slots a thread of a full workgroup
+    constexpr bool CAN = CN * 2 == CK * PV_CB_THREADS && NR <= 2048;
+    // FUSE: a group the host's parameters alone make compact (the lean pass logs nothing but dense
+    // IPv4 entries: exception entries and update-log entries are the general path's) has its ranges
+    // but the last inserted beside the Net phase, each after the range's own barriers
+    bool early = false;
+    if constexpr (FUSE) {
+        static_assert(sizeof(St) + sizeof(NetRegState) <= 160 * 1024, "pv_net_combine_plain: the Net state and the combine table in one CU's LDS");
+        constexpr uint32_t NETW = 4; // Net waves: one a SIMD, as in pv_net_kernel_reg_tc
+        const uint32_t e0 = blockIdx.x * P.cb_fan, e1 = min(e0 + P.cb_fan, P.grid_main);
+        uint64_t ea = 0, ez = 0, eb, ey = 0;
+        if (e1 > e0) { wg_records(P, e0, ea, ez); wg_records(P, e1 - 1, eb, ey); }
+#ifndef PV_FUSE_NO_EARLY
+        early = CAN && P.cb_compact && e1 > e0 + 1 && P.ip_compact && (P.net_groups & PV_NET_TOP_IPS_BIT) && blockDim.x == PV_CB_THREADS &&
+                ey - ea <= 65535;
+#endif
+        if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < NETW) {
+            net_fast_reg<NETW, true, true>(Pp);
+            // hand-over, this side: every store of the Net phase acknowledged by the L2
+            __builtin_amdgcn_s_waitcnt(PV_WAIT_VMCNT0);
+        } else {
+            // the Net phase's init barrier first (the Net waves start streaming at once), then
+            // the clear, then its other barriers, two a range and the last: parked at s_barrier, no
+            // polling. The count is the same for every wave of the workgroup.
+            // A range's log is complete at its first barrier (the Net waves wait for their stores
+            // before it).
+            const uint32_t tid = threadIdx.x - 64u * NETW, nt = blockDim.x - 64u * NETW;
+            lds_barrier();
+            comb_init<CN>(S, 2u << P.reg_log2, tid, nt);
+            for (uint32_t gr = e0; gr < e1; gr++) {
+                lds_barrier();
+                lds_barrier();
+                if (early && gr + 1 < e1)
+                    comb_crange_own<CN>(P, S, reinterpret_cast<PV_G ulonglong2 *>(P.tp_buf) + (uint64_t)e0 * P.mq_cap, gr, (uint32_t)ea, tid, nt);
+            }
+            lds_barrier();
+        }
+        __syncthreads();
+        TST_WALL(P, 2)
+    }
     // the short chain (no DNS pass, no pv_net_slow_list ahead of this kernel): a batch the Net pass
     // found a DNS message or a deferred record in is left as it is for the regular chain, which the
     // host runs next: no list, no run word, no cb_hm word, no tp_hands bit (pv_topn_merge then
     // returns at its first line)
-    if (P.plain_chain && (*P.n_dns | *P.n_slow)) return;
+    if constexpr (!FUSE) {
+        if (P.plain_chain && (*P.n_dns | *P.n_slow)) return;
+    }
     TST_DECL
     const uint32_t nreg = 2u << P.reg_log2; // run keys
     // this workgroup's grid ranges [g0, g1) (cb_fan of them): their update logs and IP logs into
     // one table, one list at the first range's place
     const uint32_t g0 = blockIdx.x * P.cb_fan, g1 = min(g0 + P.cb_fan, P.grid_main);
+    if constexpr (FUSE) {
+        // the batch's two counts are final only at the kernel's end: this workgroup looks at its
+        // own ranges' and leaves them untouched when either is set (the same value in every
+        // thread). Other workgroups may have combined theirs by then: pv_topn_merge returns at its
+        // first line on such a batch, and the regular chain's combine rewrites what they wrote.
+        uint32_t bad = 0;
+        for (uint32_t gr = g0; gr < g1; gr++) bad |= ld_own<true>(P.dq_cnt + gr) | ld_own<true>(P.slow_cnt + gr);
+        if (bad) return;
+    }
     const uint64_t wbase = (uint64_t)g0 * P.mq_cap;
     PV_G ulonglong2 *sp = reinterpret_cast<PV_G ulonglong2 *>(P.tp_buf) + wbase;
     PV_G ulonglong2 *out = reinterpret_cast<PV_G ulonglong2 *>(P.cb) + wbase;
@@ -3343,8 +3483,6 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
     // Only a workgroup of more than one range takes it: with one range the compact table was
     // measured no faster than the generic one (61.2K against 60.6K cycles a C2 workgroup, the
     // insert's gain spent on the count pass over twice the slots; profiles/r8/combine_compact)
-    constexpr uint32_t CK = 16; // compact slots a thread of a full workgroup
-    constexpr bool CAN = CN * 2 == CK * PV_CB_THREADS && NR <= 2048;
     // (the counts are read here and looked at after the table is cleared: the same words clear
     // either view)
     uint32_t cbase = 0; // the group's first record
@@ -3355,25 +3493,27 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
             wg_records(P, g0, a0, z0);
             wg_records(P, g1 - 1, a1, z1);
             other = z1 - a0 > 65535 ? 1u : 0u;
-            for (uint32_t gr = g0; gr < g1; gr++) other |= P.mq_cnt[gr] | P.ipx_cnt[gr];
+            for (uint32_t gr = g0; gr < g1; gr++) other |= ld_own<FUSE>(P.mq_cnt + gr) | ld_own<FUSE>(P.ipx_cnt + gr);
             cbase = (uint32_t)a0;
         }
     }
+    if constexpr (!FUSE) { // (fused: comb_init, before the hand-over barrier)
     for (uint32_t j = threadIdx.x; j < CN; j += blockDim.x) { S.key[j] = 0; S.cnt[j] = 0; S.rep[j] = 0xffffffffu; }
     for (uint32_t r = threadIdx.x; r < nreg; r += blockDim.x) {
         S.h[r] = 0;
         if (!(r & 1)) S.tb[r >> 1] = 0;
     }
     if (threadIdx.x == 0) S.nsp = 0;
+    }
     const bool compact = CAN && __builtin_amdgcn_readfirstlane(other) == 0;
-    __syncthreads();
+    if constexpr (!FUSE) __syncthreads();
     TST(0)
     if (compact) {
         if constexpr (CAN) {
             // the generic compact-log loop below with 4-B keys: PV_CB_U log words and direction
             // words in flight, then every first-probe key and index half, then the inserts
             const PV_G uint32_t *ip4 = P.iplog32;
-            for (uint32_t gr = g0; gr < g1; gr++) {
+            for (uint32_t gr = FUSE && early ? g1 - 1 : g0; gr < g1; gr++) {
                 uint64_t a, z;
                 wg_records(P, gr, a, z);
                 const uint32_t nn = (uint32_t)(z - a), bd = blockDim.x, ra = (uint32_t)(a - cbase);
@@ -3383,8 +3523,8 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
 #pragma unroll
                     for (int u = 0; u < PV_CB_U; u++) {
                         const uint32_t j = j0 + u * bd;
-                        ipv[u] = j < nn ? ip4[a + j] : 0u;
-                        dw[u] = j < nn ? P.ipdir[(a + j) >> 6] : 0ull;
+                        ipv[u] = j < nn ? ld_own<FUSE>(ip4 + a + j) : 0u;
+                        dw[u] = j < nn ? ld_own<FUSE>(P.ipdir + ((a + j) >> 6)) : 0ull;
                     }
                     uint32_t dir[PV_CB_U], pos[PV_CB_U], cur[PV_CB_U], rp[PV_CB_U];
 #pragma unroll
@@ -3403,7 +3543,7 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
         }
     } else
     for (uint32_t gr = g0; gr < g1; gr++) {
-    const uint32_t cnt = P.mq_cnt[gr];
+    const uint32_t cnt = ld_own<FUSE>(P.mq_cnt + gr); // (fused: the Net phase's zero)
     const PV_G uint64_t *q = P.mq + (uint64_t)gr * P.mq_cap * 2;
     batched<8>(cnt, [&](uint64_t j) { return PV_E16(q)[j]; },
                [&](uint64_t, ulonglong2 e) { comb_add<CN>(P, S, sp, e.x, (uint32_t)e.y, (uint32_t)(e.y >> 32)); });
@@ -3426,8 +3566,8 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
 #pragma unroll
                 for (int u = 0; u < PV_CB_U; u++) {
                     const uint64_t j = j0 + (uint64_t)u * bd;
-                    ipv[u] = j < nn ? ip4[a + j] : 0u;
-                    dw[u] = j < nn ? P.ipdir[(a + j) >> 6] : 0ull;
+                    ipv[u] = j < nn ? ld_own<FUSE>(ip4 + a + j) : 0u;
+                    dw[u] = j < nn ? ld_own<FUSE>(P.ipdir + ((a + j) >> 6)) : 0ull;
                 }
                 uint64_t ck[PV_CB_U], cur[PV_CB_U];
                 uint32_t pos[PV_CB_U], rp[PV_CB_U];
@@ -3443,8 +3583,9 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
                 for (int u = 0; u < PV_CB_U; u++)
                     if (ipv[u]) comb_add_pre<CN>(P, S, sp, ck[u], 1u, (uint32_t)(a + j0 + (uint64_t)u * bd), pos[u], cur[u], rp[u]);
             }
-            const uint32_t nx = P.ipx_cnt[gr];
-            for (uint32_t q = threadIdx.x; q < nx; q += blockDim.x) comb_add<CN>(P, S, sp, ipl[q], 1u, P.ipx_rep[a + q]);
+            const uint32_t nx = ld_own<FUSE>(P.ipx_cnt + gr);
+            for (uint32_t q = threadIdx.x; q < nx; q += blockDim.x)
+                comb_add<CN>(P, S, sp, ld_own<FUSE>(ipl + q), 1u, ld_own<FUSE>(P.ipx_rep + a + q));
         } else {
             batched<PV_CB_U>(z - a, [&](uint64_t j) { return ipl[j]; }, [&](uint64_t j, uint64_t e) {
                 if (e) comb_add<CN>(P, S, sp, e, 1u, (uint32_t)(a + j));
@@ -3543,6 +3684,7 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P)
 #endif
     TST(4)
     TST_FLUSH(0)
+    if constexpr (FUSE) { TST_WALL(P, 3) }
 }
 // LDS: an 8192-entry table (16384 compact slots in the same bytes) with up to 2^10 regions per
 // table, 2048 entries with more; two run keys per region
@@ -3554,6 +3696,14 @@ extern "C" __global__ void __launch_bounds__(PV_CB_THREADS) pv_topn_combine(cons
 {
     PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
     topn_combine<PV_CB_CN, 2048>(P);
+}
+// The plain short chain's Net pass and combine as one launch, one workgroup a CU (the host's
+// conditions: pv_host.cpp). No other workgroup's data is read, so nothing grid-wide separates the
+// two phases: a barrier of the workgroup's own.
+extern "C" __global__ void __launch_bounds__(PV_CB_THREADS) pv_net_combine_plain(const PvParams *__restrict__ Pp)
+{
+    PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
+    topn_combine<PV_CB_CN, 2048, true>(P, Pp);
 }
 extern "C" __global__ void __launch_bounds__(PV_CB_THREADS) pv_topn_combine_r12(const PvParams *__restrict__ Pp)
 {
@@ -3608,6 +3758,9 @@ extern "C" __global__ void __launch_bounds__(PV_MG_THREADS) __attribute__((amdgp
     const uint32_t rk = blockIdx.x;                  // run key: handler << reg_log2 | region
     const uint32_t r = rk & ((1u << P.reg_log2) - 1);
     const uint32_t hd = rk >> P.reg_log2;            // 0 Net tables, 1 DNS tables
+    // (a short-chain batch the guess was wrong about: a fused combine's other workgroups may have
+    // listed their ranges before the two counts were final; the regular chain runs next)
+    if (P.plain_chain && (*P.n_dns | *P.n_slow)) return;
     if (!((*P.tp_hands >> hd) & 1)) return; // no entry of this handler in the batch
     if (P.xmerge && (r < P.x_lo || r >= P.x_hi)) return; // (multi-GPU owner merge: this rank's regions)
     __shared__ MergeRuns U;

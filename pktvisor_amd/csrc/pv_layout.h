@@ -470,7 +470,9 @@ struct PvParams {
                   // 16 no DNS name decode, 32 no DNS table updates
     uint32_t plain_chain; // the short chain (the host guessed a batch without DNS messages or deferred records
                           // and launched neither pass): pv_topn_combine returns untouched when *n_dns or
-                          // *n_slow says otherwise, and the host then runs the regular chain
+                          // *n_slow says otherwise (a workgroup of pv_net_combine_plain: when its own ranges'
+                          // counts do), pv_topn_merge returns at its first line, and the host then runs the
+                          // regular chain
     PV_G uint32_t *flags;
     // DNS v1 filters (DnsStreamHandler::_filtering, dns/v1/DnsStreamHandler.cpp:538-648)
     uint32_t f_flags, f_rcode_mask, f_ancount, f_nq;
@@ -501,6 +503,8 @@ struct PvParams {
     const PV_G uint64_t *gfilt;
     uint32_t dpos[PV_MAX_SHIFTS];      // span-relative ord of the event that shifts DNS period k+1
     PV_G const uint32_t *psl;          // public_suffix_list table (PVDF_PSL)
+    uint32_t net_contig; // diagnostic builds (-DPV_RANGE_AB, PV_NET_CONTIG=1 in the environment): lean Net workgroup b
+                         // walks ranges [b * cb_fan, (b + 1) * cb_fan) instead of b, b + G, b + 2G
 };
 
 // pv_fill_multi's segment list (kernel argument)
