@@ -724,6 +724,39 @@ int pv_set_dhcp(pv_ctx *ctx, const pv_dhcp_config *cfg);
 /* Device time of pv_dhcp_scan, as pv_kernel_timing gives the Net pass's: summed over the batches
  * processed while pv_set_kernel_timing is on (every batch's scan is stamped). */
 int pv_dhcp_timing(pv_ctx *ctx, double *scan_ms, uint64_t *launches, int reset);
+
+/* ---- The BGP handler (BgpStreamHandler, src/handlers/bgp): the "bgp" schema. The reference's
+ * handler listens to the pcap input's TCP reassembly and counts each chunk of in-order data it
+ * delivers on a connection with port 179 on either side, by the type of the chunk's first BGP
+ * message (byte 18). While the handler is attached every batch gets one more device pass
+ * (pv_bgp_scan: one lane per record; per 64-record tile a 64-bit mask of the TCP/179 segments and
+ * the greatest seconds value of the tile's TCP records of any port, which drive the reassembly's
+ * 30 s time-outs). The segments are written on the device in record order with their payload
+ * bytes (pv_bgp_decode) and the host manager replays them: TcpReassembly's rules per connection
+ * (open connections and held fragments live across batches), the LRU time-outs, its own window
+ * (shifted by its own events; pv_set_start_tstamp, pv_set_end_tstamp and pv_check_period_shift
+ * reach it) and its own jsf32 deep-sampling draws. With pv_set_end_of_capture armed the final
+ * batch ends with closeAllConnections. The other passes and their outputs do not change. A batch
+ * with more than max_events segments is decoded in rounds; nothing is dropped.
+ * Outputs: pv_window_json gains a "bgp" object (period, wire_packets.{events, deep_samples, open,
+ * update, notification, keepalive, routerefresh, total, filtered}; filtered is always 0, the
+ * handler has no filters; rates are not kept); pv_window_prometheus takes PV_HANDLER_BGP.
+ * Definitions where the reference has none: a delivered chunk shorter than 19
+ * bytes or with a type outside 1..5 is no event; only port-179 connections are kept; a closed
+ * connection's key is ignored for 300 event seconds, then forgotten.
+ * Refused with PV_EUNSUPPORTED and a message naming BGP: pv_window_opentelemetry and
+ * pv_bucket_merge with PV_HANDLER_BGP; pv_process_dnstap while attached (the reference's
+ * "BgpStreamHandler: unsupported input event proxy"); sharded runs (pktvisor_amd.dist). */
+#define PV_HANDLER_BGP 8u
+typedef struct pv_bgp_config {
+    uint32_t recorded_stream; /* "recorded_stream" (period lengths are the stream's either way) */
+    uint32_t max_events;      /* segments a decode round stores; 0 => min(max_records, 1 << 20) */
+} pv_bgp_config;
+/* Call before the first batch (or after pv_reset); NULL detaches. Allocates every device buffer of
+ * the stage, so a steady-state batch allocates nothing. */
+int pv_set_bgp(pv_ctx *ctx, const pv_bgp_config *cfg);
+/* Device time of pv_bgp_scan, as pv_dhcp_timing gives pv_dhcp_scan's. */
+int pv_bgp_timing(pv_ctx *ctx, double *scan_ms, uint64_t *launches, int reset);
 /* pv_geodb_hash of the attached city and ASN databases (0: none): what the ranks of a sharded run
  * compare before they sum their windows. pv_comm_allreduce_window compares them itself; a caller
  * that moves the pv_window_regions words with its own transport compares these first. */

@@ -72,6 +72,10 @@ class pv_dhcp_config(ctypes.Structure):
     _fields_ = [("xact_ttl_ms", ctypes.c_uint32), ("recorded_stream", ctypes.c_uint32), ("max_events", ctypes.c_uint32)]
 
 
+class pv_bgp_config(ctypes.Structure):
+    _fields_ = [("recorded_stream", ctypes.c_uint32), ("max_events", ctypes.c_uint32)]
+
+
 from pktvisor_amd.config import ConfigException as ConfigError  # noqa: E402  (the reference's texts)
 from pktvisor_amd.config import StreamHandlerException  # noqa: E402,F401
 
@@ -188,12 +192,12 @@ EXPORTS = ["pv_version", "pv_device_count", "pv_create", "pv_destroy", "pv_last_
            "pv_topn_x_candidates", "pv_topn_x_names", "pv_topn_x_view", "pv_values_x_select", "pv_comm_values_select",
            "pv_slow_x_finish", "pv_comm_slow_finish", "pv_geodb_open", "pv_geodb_open_file", "pv_geodb_close",
            "pv_geodb_last_error", "pv_geodb_entries", "pv_geodb_hash", "pv_geodb_hashes", "pv_set_net_filters", "pv_geodb_entry", "pv_geodb_lookup", "pv_set_geodb",
-           "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing", "pv_chain_stats", "pv_fuse_stats"]
+           "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing", "pv_set_bgp", "pv_bgp_timing", "pv_chain_stats", "pv_fuse_stats"]
 PV_GEODB_CITY, PV_GEODB_ASN = 0, 1
 # pv_allreduce_fn: (uint64_t *buf, size_t n, int op, void *user) -> int
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
-PV_HANDLER_NET, PV_HANDLER_DNS, PV_HANDLER_DHCP = 1, 2, 4
-_HANDLER_BITS = {"net": PV_HANDLER_NET, "dns": PV_HANDLER_DNS, "dhcp": PV_HANDLER_DHCP}
+PV_HANDLER_NET, PV_HANDLER_DNS, PV_HANDLER_DHCP, PV_HANDLER_BGP = 1, 2, 4, 8
+_HANDLER_BITS = {"net": PV_HANDLER_NET, "dns": PV_HANDLER_DNS, "dhcp": PV_HANDLER_DHCP, "bgp": PV_HANDLER_BGP}
 PV_PERIOD_AUTO = 0xFFFFFFFF
 PART_NET, PART_DNS = 0, 1
 PV_REDUCE_SUM, PV_REDUCE_MIN = 0, 1
@@ -379,6 +383,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.pv_geodb_lookup_device.argtypes = [P, U32, P, ctypes.c_size_t, U32, P]
     lib.pv_set_dhcp.argtypes = [P, ctypes.POINTER(pv_dhcp_config)]
     lib.pv_dhcp_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.c_int]
+    lib.pv_set_bgp.argtypes = [P, ctypes.POINTER(pv_bgp_config)]
+    lib.pv_bgp_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.c_int]
     if hasattr(lib, "pv_chain_stats"):  # (diagnostics only: a PVGPU_LIB build of an older tree, for A/B runs, has none)
         lib.pv_chain_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.c_int]
     if hasattr(lib, "pv_fuse_stats"):  # (the same)
@@ -704,10 +710,11 @@ class PvHandlers:
                  net2_config: Optional[dict] = None, dns2_config: Optional[dict] = None,
                  deep_sample_rate: int = 100, tcp_packet_reassembly_cache_limit: int = 0, bpf=None,
                  tcp_exact_lru: bool = False, geo_city_db=None, geo_asn_db=None, dhcp_config: Optional[dict] = None,
-                 dhcp_max_events: int = 0):
+                 dhcp_max_events: int = 0, bgp_config: Optional[dict] = None, bgp_max_events: int = 0):
         """dhcp_config: attaches the DHCP handler ("dhcp" schema, DhcpStreamHandler) with its config
         map (recorded_stream, xact_ttl_secs, xact_ttl_ms, the window keys); dhcp_max_events: the DHCP
-        events one decode round stores (0: the default)."""
+        events one decode round stores (0: the default). bgp_config / bgp_max_events: the same for
+        the BGP handler ("bgp" schema, BgpStreamHandler; recorded_stream and the window keys)."""
         from pktvisor_amd import config as pvcfg
         self.lib = load_library()
         filt = dns_filter_config(dns_filters) if dns_filters else None
@@ -730,9 +737,11 @@ class PvHandlers:
             if d2["xact_ttl_ms"] is not None:
                 xact_ttl_ms = d2["xact_ttl_ms"]
         dhcp = pvcfg.dhcp_start(dict(dhcp_config)) if dhcp_config is not None else None
+        bgp = pvcfg.bgp_start(dict(bgp_config)) if bgp_config is not None else None
         if net_config is not None or dns_config is not None or net2_config is not None or dns2_config is not None:
             ncfg, dcfg = dict(net_config or {}), dict(dns_config or {})
-            win = pvcfg.window_config([ncfg, dcfg, dict(net2_config or {}), dict(dns2_config or {}), dict(dhcp_config or {})])
+            win = pvcfg.window_config([ncfg, dcfg, dict(net2_config or {}), dict(dns2_config or {}), dict(dhcp_config or {}),
+                                       dict(bgp_config or {})])
             deep_sample_rate = win.get("deep_sample_rate", deep_sample_rate)
             num_periods = win.get("num_periods", num_periods)
             topn_count = win.get("topn_count", topn_count)
@@ -750,9 +759,9 @@ class PvHandlers:
                 self.dnstap_mask = d["dnstap_mask"]
             if d["xact_ttl_ms"] is not None and dns2_config is None:
                 xact_ttl_ms = d["xact_ttl_ms"]
-        elif dhcp_config is not None:
-            # the DHCP handler alone carries window keys: the other handlers keep their keyword form
-            win = pvcfg.window_config([dict(dhcp_config)])
+        elif dhcp_config is not None or bgp_config is not None:
+            # the DHCP / BGP handlers alone carry window keys: the other handlers keep their keyword form
+            win = pvcfg.window_config([dict(dhcp_config or {}), dict(bgp_config or {})])
             deep_sample_rate = win.get("deep_sample_rate", deep_sample_rate)
             num_periods = win.get("num_periods", num_periods)
             topn_count = win.get("topn_count", topn_count)
@@ -808,6 +817,22 @@ class PvHandlers:
         self.dhcp_attached = False
         if dhcp is not None:
             self.set_dhcp(dhcp["xact_ttl_ms"], dhcp["recorded_stream"], dhcp_max_events)
+
+        self.bgp_attached = False
+        if bgp is not None:
+            self.set_bgp(bgp["recorded_stream"], bgp_max_events)
+
+    def set_bgp(self, recorded_stream: bool = False, max_events: int = 0):
+        """attach the BGP handler (pv_set_bgp): window_json then carries "bgp". Before the first batch."""
+        cfg = pv_bgp_config(int(bool(recorded_stream)), int(max_events))
+        self._check(self.lib.pv_set_bgp(self.ctx, ctypes.byref(cfg)), "pv_set_bgp")
+        self.bgp_attached = True
+
+    def bgp_timing(self, reset: bool = False):
+        """(ms, launches) of pv_bgp_scan over the batches processed while set_kernel_timing is on"""
+        ms, n = ctypes.c_double(), ctypes.c_uint64()
+        self._check(self.lib.pv_bgp_timing(self.ctx, ctypes.byref(ms), ctypes.byref(n), int(reset)), "pv_bgp_timing")
+        return ms.value, n.value
 
     def set_dhcp(self, xact_ttl_ms: int = 0, recorded_stream: bool = False, max_events: int = 0):
         """attach the DHCP handler (pv_set_dhcp): window_json then carries "dhcp". Before the first batch."""
@@ -1017,7 +1042,7 @@ class PvHandlers:
 
     def window_prometheus(self, period: int = 0, labels: Optional[dict] = None, handlers: str = "net,dns") -> str:
         """StreamHandler::window_prometheus (src/AbstractMetricsManager.h:506-531): the
-        Prometheus text of bucket `period` of the named handlers ("net", "dns", "dhcp"), with
+        Prometheus text of bucket `period` of the named handlers ("net", "dns", "dhcp", "bgp"), with
         `labels` added to every sample."""
         hmask = sum(_HANDLER_BITS[x] for x in handlers.split(","))
         labels = labels or {}

@@ -184,6 +184,16 @@ def dhcp_start(cfg: dict) -> dict:
     return {"recorded_stream": "recorded_stream" in cfg, "xact_ttl_ms": ttl}
 
 
+BGP_CONFIG_DEFS = ("recorded_stream",)
+
+
+def bgp_start(cfg: dict) -> dict:
+    """BgpStreamHandler::start (src/handlers/bgp/BgpStreamHandler.cpp:21-43) up to the signal
+    wiring: {"recorded_stream": bool}. The handler has no metric groups and no filters."""
+    validate_configs(cfg, BGP_CONFIG_DEFS)
+    return {"recorded_stream": "recorded_stream" in cfg}
+
+
 # Net v2 (src/handlers/net/v2/NetStreamHandler.h:25-31,262-267; defaults :47-52)
 NET2_GROUP_DEFS = {"cardinality": 1 << 1, "counters": 1 << 0, "quantiles": 1 << 2, "top_geo": 1 << 3, "top_ips": 1 << 4}
 NET2_DEFAULT_GROUPS = ("counters", "cardinality", "quantiles", "top_geo", "top_ips")

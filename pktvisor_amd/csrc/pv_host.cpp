@@ -177,6 +177,7 @@ int ensure_started(pv_ctx *c, int64_t sec, int64_t nsec)
     // (the DHCP manager hears the input's start_tstamp_signal too: the batch's first record,
     // not its first DHCP packet)
     if (c->dhcp) c->dhcp->set_start(sec, nsec);
+    if (c->bgp) c->bgp->set_start(sec, nsec);
     c->started = true;
     return 0;
 }
@@ -253,6 +254,7 @@ void mark_merged(pv_ctx *c, const char *by)
 }
 } // namespace pvh
 static void dhcp_free(pv_ctx *c);
+static void bgp_free(pv_ctx *c);
 static int merged_refuse(pv_ctx *c)
 {
     if (!c->merged) return 0;
@@ -800,6 +802,7 @@ void pv_destroy(pv_ctx *c)
                     c->d_foffs, c->d_fsc, c->d_fscan, c->d_eoc, c->d_eoc_cnt};
     for (void *p : ptrs) if (p) hipFree(p);
     dhcp_free(c);
+    bgp_free(c);
     for (void *p : {(void *)c->d_nf_pass[0], (void *)c->d_nf_pass[1], (void *)c->d_gfilt}) if (p) hipFree(p);
     for (auto &g : c->geo) {
         if (g.d_tree) hipFree(g.d_tree);
@@ -861,6 +864,7 @@ int pv_reset(pv_ctx *c)
     }
     c->started = c->ended = false;
     if (c->dhcp) c->dhcp->reset();
+    if (c->bgp) c->bgp->reset();
     c->records_seen = 0;
     c->seen_hi = 0; // (every slot is cleared before its next use: no entry keeps a seen flag)
     c->seen_off = false;
@@ -2914,6 +2918,134 @@ extern "C" int pv_chain_stats(pv_ctx *c, uint64_t out[4], int reset)
     return 0;
 }
 
+// The BGP handler's device stage on a batch (pv_bgp.hip) and the host replay of what it finds: the
+// scan's per-tile masks, counts and TCP seconds, the counts' exclusive scan (each tile's rank base)
+// and the seconds' prefix maximum, then rounds of at most bgp_cap segments: decode, copy back,
+// reassemble in record order. A round whose payload bytes do not fit the arena is rerun over half
+// the ranks (a single segment always fits), so nothing is dropped. The caller holds c->mu.
+static int bgp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, const pv_index_info *info, hipStream_t st)
+{
+    hipError_t e;
+    const uint32_t n = (uint32_t)info->n_records, ntiles = (n + 63) / 64;
+    // (both scans' temporary storage was sized for max_records at attach time: this grows nothing)
+    size_t tb = 0, tb2 = 0;
+    if (!hip_ok(e = pv_exclusive_scan_u32(nullptr, &tb, nullptr, nullptr, ntiles, st)) ||
+        !hip_ok(e = pv_bgp_prefix_max(nullptr, &tb2, nullptr, nullptr, ntiles, st)))
+        return c->hipfail(e, "BGP scan size");
+    if (int rc = x_grow_dev(c, &c->d_bg_scan, c->bg_scan_bytes, std::max(tb, tb2), "BGP scan")) return rc;
+    const uint32_t grid = std::max(1u, std::min((ntiles + 3) / 4, (uint32_t)c->cus * 8));
+    const bool timed = c->timing_every != 0;
+    if (timed) hipEventRecord(c->ev_start, st);
+    hipLaunchKernelGGL(pv_bgp_scan, dim3(grid), dim3(256), 0, st, d_recs, d_offs, n, c->cfg.linktype, c->cfg.ts_nano,
+                       (const PvParams *)c->d_bg_params, c->d_bg_mask, c->d_bg_cnt, c->d_bg_tsec);
+    if (!hip_ok(e = hipGetLastError())) return c->hipfail(e, "launch pv_bgp_scan");
+    if (timed) hipEventRecord(c->ev_stop, st);
+    tb = c->bg_scan_bytes;
+    uint32_t tail[3] = {0, 0, 0};
+    if (!hip_ok(e = pv_exclusive_scan_u32(c->d_bg_scan, &tb, c->d_bg_cnt, c->d_bg_rank, ntiles, st))) return c->hipfail(e, "BGP scan");
+    tb = c->bg_scan_bytes;
+    if (!hip_ok(e = pv_bgp_prefix_max(c->d_bg_scan, &tb, c->d_bg_tsec, c->d_bg_tincl, ntiles, st)) ||
+        !hip_ok(e = hipMemcpyAsync(&tail[0], c->d_bg_rank + ntiles - 1, 4, hipMemcpyDeviceToHost, st)) ||
+        !hip_ok(e = hipMemcpyAsync(&tail[1], c->d_bg_cnt + ntiles - 1, 4, hipMemcpyDeviceToHost, st)) ||
+        !hip_ok(e = hipMemcpyAsync(&tail[2], c->d_bg_tincl + ntiles - 1, 4, hipMemcpyDeviceToHost, st)) ||
+        !hip_ok(e = hipStreamSynchronize(st)))
+        return c->hipfail(e, "BGP scan");
+    if (timed) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->ev_start, c->ev_stop) == hipSuccess) { c->bgp_scan_ms += ms; c->bgp_scan_launches++; }
+    }
+    const uint32_t total = tail[0] + tail[1];
+    uint32_t kmax = c->bgp_cap; // (a round that did not fit its arena lowers it for the batch's later rounds)
+    for (uint32_t base = 0; base < total;) {
+        uint32_t k = std::min(kmax, total - base);
+        unsigned long long top = 0;
+        for (;;) {
+            if (!hip_ok(e = hipMemsetAsync(c->d_bg_top, 0, 8, st))) return c->hipfail(e, "BGP decode");
+            hipLaunchKernelGGL(pv_bgp_decode, dim3((n + 255) / 256), dim3(256), 0, st, d_recs, d_offs, n, c->cfg.linktype,
+                               c->cfg.ts_nano, (const PvParams *)c->d_bg_params, (const unsigned long long *)c->d_bg_mask,
+                               (const uint32_t *)c->d_bg_rank, (const uint32_t *)c->d_bg_tincl, base, k, c->d_bg_seg, c->d_bg_arena,
+                               c->bgp_arena_cap, c->d_bg_top);
+            if (!hip_ok(e = hipGetLastError())) return c->hipfail(e, "launch pv_bgp_decode");
+            if (!hip_ok(e = hipMemcpyAsync(&top, c->d_bg_top, 8, hipMemcpyDeviceToHost, st)) || !hip_ok(e = hipStreamSynchronize(st)))
+                return c->hipfail(e, "BGP decode");
+            if (top <= c->bgp_arena_cap || k == 1) break;
+            k = (k + 1) / 2;
+            kmax = k;
+        }
+        if (top > c->bgp_arena_cap) return c->fail(PV_EINVAL, "BGP decode: a segment of %llu bytes", top); // (not reached: <= 65,535)
+        c->h_bg_seg.resize(k);
+        c->h_bg_arena.resize((size_t)top);
+        if (!hip_ok(e = hipMemcpyAsync(c->h_bg_seg.data(), c->d_bg_seg, (size_t)k * sizeof(PvBgpSeg), hipMemcpyDeviceToHost, st)) ||
+            (top && !hip_ok(e = hipMemcpyAsync(c->h_bg_arena.data(), c->d_bg_arena, (size_t)top, hipMemcpyDeviceToHost, st))) ||
+            !hip_ok(e = hipStreamSynchronize(st)))
+            return c->hipfail(e, "BGP segments");
+        c->bgp->replay(c->h_bg_seg.data(), k, c->h_bg_arena.data(), (size_t)top);
+        base += k;
+    }
+    c->bgp->end_batch(tail[2]);
+    // the capture's final batch (pv_set_end_of_capture): TcpReassembly::closeAllConnections
+    if (c->eoc_batch) c->bgp->close_all();
+    return 0;
+}
+
+static void bgp_free(pv_ctx *c)
+{
+    for (void *p : {(void *)c->d_bg_mask, (void *)c->d_bg_top, (void *)c->d_bg_cnt, (void *)c->d_bg_rank, (void *)c->d_bg_tsec,
+                    (void *)c->d_bg_tincl, (void *)c->d_bg_seg, (void *)c->d_bg_arena, (void *)c->d_bg_params, c->d_bg_scan})
+        if (p) hipFree(p);
+    c->d_bg_mask = c->d_bg_top = nullptr;
+    c->d_bg_cnt = c->d_bg_rank = c->d_bg_tsec = c->d_bg_tincl = nullptr;
+    c->d_bg_seg = nullptr;
+    c->d_bg_arena = nullptr;
+    c->d_bg_params = nullptr;
+    c->d_bg_scan = nullptr;
+    c->bg_scan_bytes = 0;
+    c->bgp.reset();
+}
+
+// BgpStreamHandler's constructor and start() (BgpStreamHandler.cpp:10-43) on this context's pcap
+// input: the manager with the context's window config, and every device buffer of the stage
+extern "C" int pv_set_bgp(pv_ctx *c, const pv_bgp_config *cfg)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    if (c->started) return c->fail(PV_EINVAL, "pv_set_bgp: call before the first batch");
+    hipSetDevice(c->device);
+    bgp_free(c);
+    if (!cfg) return 0;
+    c->bgp_cfg = *cfg;
+    const uint64_t maxn = std::max<uint64_t>(1, c->max_records);
+    const uint64_t cap = std::min<uint64_t>(cfg->max_events ? cfg->max_events : std::min<uint64_t>(maxn, 1u << 20), 1u << 22);
+    c->bgp_cap = (uint32_t)cap;
+    // the arena: 128 bytes a segment of a full round (a KEEPALIVE is 19, most UPDATEs are below 100),
+    // never less than one segment of the greatest length
+    c->bgp_arena_cap = (uint32_t)std::max<uint64_t>(PV_BGP_ARENA_MIN, std::min<uint64_t>(cap * 128, 1u << 26));
+    const size_t ntiles = (size_t)((maxn + 63) / 64);
+    hipError_t e;
+    size_t tb = 0, tb2 = 0;
+    if (!hip_ok(e = hipMalloc(&c->d_bg_mask, ntiles * 8)) || !hip_ok(e = hipMalloc(&c->d_bg_cnt, ntiles * 4)) ||
+        !hip_ok(e = hipMalloc(&c->d_bg_rank, ntiles * 4)) || !hip_ok(e = hipMalloc(&c->d_bg_tsec, ntiles * 4)) ||
+        !hip_ok(e = hipMalloc(&c->d_bg_tincl, ntiles * 4)) || !hip_ok(e = hipMalloc(&c->d_bg_top, 256)) ||
+        !hip_ok(e = hipMalloc(&c->d_bg_seg, cap * sizeof(PvBgpSeg))) || !hip_ok(e = hipMalloc(&c->d_bg_arena, c->bgp_arena_cap)) ||
+        !hip_ok(e = hipMalloc(&c->d_bg_params, sizeof(PvParams))) || !hip_ok(e = hipMemset(c->d_bg_params, 0, sizeof(PvParams))) ||
+        !hip_ok(e = pv_exclusive_scan_u32(nullptr, &tb, nullptr, nullptr, ntiles, c->stream)) ||
+        !hip_ok(e = pv_bgp_prefix_max(nullptr, &tb2, nullptr, nullptr, ntiles, c->stream))) {
+        bgp_free(c);
+        return c->hipfail(e, "BGP stage buffers");
+    }
+    if (int rc = x_grow_dev(c, &c->d_bg_scan, c->bg_scan_bytes, std::max(tb, tb2), "BGP scan")) { bgp_free(c); return rc; }
+    c->bgp.reset(new pvbgp::Manager(c->cfg.num_periods, c->cfg.deep_sample_rate));
+    return 0;
+}
+
+extern "C" int pv_bgp_timing(pv_ctx *c, double *scan_ms, uint64_t *launches, int reset)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    if (scan_ms) *scan_ms = c->bgp_scan_ms;
+    if (launches) *launches = c->bgp_scan_launches;
+    if (reset) { c->bgp_scan_ms = 0; c->bgp_scan_launches = 0; }
+    return 0;
+}
+
 int pv_process_device(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, const pv_index_info *info,
                       const uint32_t *sc_idx, const uint32_t *sc_sec, void *stream)
 {
@@ -2956,6 +3088,10 @@ int pv_process_device(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, 
     if (c->dhcp) {
         // the DHCP handler's own pass over the batch (the Net and DNS passes below know nothing of it)
         if (int rc = dhcp_stage(c, d_recs, d_offs, info, st)) return rc;
+    }
+    if (c->bgp) {
+        // the BGP handler's own pass, as independent of the others
+        if (int rc = bgp_stage(c, d_recs, d_offs, info, st)) return rc;
     }
     std::vector<Shift> nsh, dsh;
     if (int rc = batch_shifts(c, d_recs, d_offs, info, sc_idx, sc_sec, st, nsh, dsh)) return rc;
@@ -3341,6 +3477,8 @@ int pv_process_dnstap(pv_ctx *c, const uint8_t *buf, size_t bytes, uint32_t msg_
     if (c->geo[0].on || c->geo[1].on) return c->fail(PV_EUNSUPPORTED, "geo databases: the dnstap input's geo metrics are not built");
     // DhcpStreamHandler's constructor takes a pcap input only (DhcpStreamHandler.cpp:9-18)
     if (c->dhcp) return c->fail(PV_EUNSUPPORTED, "DhcpStreamHandler: unsupported input event proxy dnstap (the DHCP handler is attached)");
+    // and so does BgpStreamHandler's (BgpStreamHandler.cpp:10-19)
+    if (c->bgp) return c->fail(PV_EUNSUPPORTED, "BgpStreamHandler: unsupported input event proxy dnstap (the BGP handler is attached)");
     hipSetDevice(c->device);
     std::vector<pvi::DtMessage> msgs;
     uint32_t frames = 0;
@@ -4058,6 +4196,7 @@ int pv_set_end_tstamp(pv_ctx *c, int64_t sec, int64_t nsec)
     c->net.meta[c->net.slots.front()].set_read_only(sec, nsec);
     c->dns.meta[c->dns.slots.front()].set_read_only(sec, nsec);
     if (c->dhcp) c->dhcp->set_end(sec, nsec);
+    if (c->bgp) c->bgp->set_end(sec, nsec);
     c->ended = true;
     return 0;
 }
@@ -4081,6 +4220,7 @@ int pv_check_period_shift(pv_ctx *c, int64_t sec, int64_t nsec)
         win_shift(c, c->net, sec, nsec);
     }
     if (c->dhcp) c->dhcp->check_period_shift(sec, nsec);
+    if (c->bgp) c->bgp->check_period_shift(sec, nsec);
     if (sec < c->dns.next_shift_sec) return 0;
     return dns_period_shift(c, sec, nsec);
 }

@@ -43,6 +43,7 @@
 #include "pv_geodb.h"
 #include "pv_layout.h"
 #include "pv_dhcp.h"
+#include "pv_bgp.h"
 
 // The kernel's name fingerprint (pv_parse.h NameStats + fp56), compiled for the host so
 // pv_set_dns_filters can key "only_qname" names exactly as the DNS pass keys first-query names.
@@ -179,6 +180,14 @@ extern "C" __global__ void pv_dhcp_scan(const uint8_t *recs, const uint32_t *off
 extern "C" __global__ void pv_dhcp_decode(const uint8_t *recs, const uint32_t *offs, uint32_t n, uint32_t linktype, uint32_t ts_nano,
                                           const PvParams *P, const unsigned long long *mask, const uint32_t *rank, uint32_t base,
                                           uint32_t cap, PvDhcpEvent *ev, uint8_t *arena, uint32_t arena_cap, uint32_t *arena_top);
+// the BGP handler's device stage (pv_bgp.hip)
+extern "C" __global__ void pv_bgp_scan(const uint8_t *recs, const uint32_t *offs, uint32_t n, uint32_t linktype, uint32_t ts_nano,
+                                       const PvParams *P, unsigned long long *mask, uint32_t *cnt, uint32_t *tsec);
+extern "C" hipError_t pv_bgp_prefix_max(void *tmp, size_t *tmp_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s);
+extern "C" __global__ void pv_bgp_decode(const uint8_t *recs, const uint32_t *offs, uint32_t n, uint32_t linktype, uint32_t ts_nano,
+                                         const PvParams *P, const unsigned long long *mask, const uint32_t *rank, const uint32_t *tincl,
+                                         uint32_t base, uint32_t cap, PvBgpSeg *seg, uint8_t *arena, uint32_t arena_cap,
+                                         unsigned long long *arena_top);
 extern "C" __global__ void pv_topn_xcount(const PvParams *P, PvXTabs T, uint32_t *cnt);
 extern "C" __global__ void pv_topn_xscan(uint32_t reg_log2, uint32_t W, const uint32_t *cnt, uint32_t *off, uint32_t *hdr);
 extern "C" __global__ void pv_topn_xwrite(const PvParams *P, PvXTabs T, const uint32_t *off, ulonglong2 *out);
@@ -935,6 +944,25 @@ struct pv_ctx {
     {
         return fail(PV_EHIP, "%s: %s", what, hipGetErrorString(e));
     }
+    // The BGP handler (pv_set_bgp; null = not attached), laid out as the DHCP handler's and kept at
+    // the context's end (no field the other passes use moves): its host manager and the device
+    // stage's buffers, all allocated at attach time: per-tile masks, counts, rank bases, TCP seconds
+    // and their prefix maximum for max_records, a round's segments and payload arena, a zeroed
+    // PvParams, the two scans' temporary storage
+    std::unique_ptr<pvbgp::Manager> bgp;
+    pv_bgp_config bgp_cfg{};
+    uint32_t bgp_cap = 0, bgp_arena_cap = 0; // segments a round stores, bytes of its arena
+    unsigned long long *d_bg_mask = nullptr, *d_bg_top = nullptr;
+    uint32_t *d_bg_cnt = nullptr, *d_bg_rank = nullptr, *d_bg_tsec = nullptr, *d_bg_tincl = nullptr;
+    PvBgpSeg *d_bg_seg = nullptr;
+    uint8_t *d_bg_arena = nullptr;
+    PvParams *d_bg_params = nullptr;
+    void *d_bg_scan = nullptr;
+    size_t bg_scan_bytes = 0;
+    std::vector<PvBgpSeg> h_bg_seg;
+    std::vector<uint8_t> h_bg_arena;
+    double bgp_scan_ms = 0; // stamped pv_bgp_scan launches (pv_set_kernel_timing)
+    uint64_t bgp_scan_launches = 0;
 };
 
 // PV_HOST_PROF mark k: host time since the previous mark goes to hprof[k]

@@ -1235,6 +1235,23 @@ void dhcp_metrics(pv_ctx *c, Prom &p, const pvdhcp::Bucket &b)
     p.topn("dhcp_top_servers", "server", "Top DHCP servers", {b.servers.begin(), b.servers.end()}, topn, pct);
 }
 
+// BgpMetricsBucket::to_prometheus (src/handlers/bgp/BgpStreamHandler.cpp:168-190); names and
+// descriptions from BgpStreamHandler.h:47-67 (the rates write nothing)
+void bgp_metrics(Prom &p, const pvbgp::Bucket &b)
+{
+    using namespace pvbgp;
+    p.gauge("bgp_wire_packets_events", "Total BGP wire packets events", b.c[C_EVENTS]);
+    p.gauge("bgp_wire_packets_deep_samples", "Total BGP wire packets that were sampled for deep inspection", b.c[C_DEEP]);
+    p.gauge("bgp_wire_packets_open", "Total BGP packets with message type OPEN", b.c[C_OPEN]);
+    p.gauge("bgp_wire_packets_update", "Total BGP packets with message type UPDATE", b.c[C_UPDATE]);
+    p.gauge("bgp_wire_packets_notification", "Total BGP packets with message type NOTIFICATION", b.c[C_NOTIFICATION]);
+    p.gauge("bgp_wire_packets_keepalive", "Total BGP packets with message type KEEPALIVE", b.c[C_KEEPALIVE]);
+    p.gauge("bgp_wire_packets_routerefresh", "Total BGP packets with message type ROUTEREFRESH", b.c[C_ROUTEREFRESH]);
+    p.gauge("bgp_wire_packets_total", "Total BGP wire packets matching the configured filter(s)", b.c[C_TOTAL]);
+    p.gauge("bgp_wire_packets_filtered", "Total BGP wire packets seen that did not match the configured filter(s) (if any)",
+            b.c[C_FILTERED]);
+}
+
 // KLL inclusive rank rule on exact data
 } // namespace pvh
 
@@ -1283,6 +1300,15 @@ int pv_window_json(pv_ctx *c, uint32_t period, int merged, char **out)
         j.key("dhcp");
         j.sep();
         j.s += pvdhcp::Manager::json(b, c->cfg.topn_count, c->cfg.topn_percentile_threshold);
+    }
+    if (c->bgp) {
+        // and the BGP handler's (pv_bgp.cpp)
+        pvbgp::Bucket b;
+        std::string err;
+        if (!c->bgp->window(period, merged != 0, b, err)) return c->fail(PV_EINVAL, "%s", err.c_str());
+        j.key("bgp");
+        j.sep();
+        j.s += pvbgp::Manager::json(b);
     }
     j.end_obj();
     *out = strdup(j.s.c_str());
@@ -1375,6 +1401,7 @@ extern "C" {
 int pv_bucket_merge(pv_ctx *c, uint32_t handler, pv_bucket **bucket, uint32_t period, int prometheus, int merged)
 {
     if (handler == PV_HANDLER_DHCP) return c->fail(PV_EUNSUPPORTED, "bucket merge: external buckets are not built for the DHCP handler");
+    if (handler == PV_HANDLER_BGP) return c->fail(PV_EUNSUPPORTED, "bucket merge: external buckets are not built for the BGP handler");
     if (!bucket || (handler != PV_HANDLER_NET && handler != PV_HANDLER_DNS)) return c->fail(PV_EINVAL, "bucket merge: one handler");
     std::lock_guard<std::mutex> g(c->mu); // values drained under the lock (pv_window_json)
     int rc = sync_xvals(c);
@@ -1541,6 +1568,13 @@ int pv_window_prometheus(pv_ctx *c, uint32_t period, uint32_t handlers, const ch
         if (!c->dhcp->window(dper, false, b, err)) return c->fail(PV_EINVAL, "%s", err.c_str());
         dhcp_metrics(c, p, b);
     }
+    if ((handlers & PV_HANDLER_BGP) && c->bgp) {
+        pvbgp::Bucket b;
+        std::string err;
+        const uint32_t bper = period != PV_PERIOD_AUTO ? period : (c->bgp->periods() > 1 ? 1u : 0u);
+        if (!c->bgp->window(bper, false, b, err)) return c->fail(PV_EINVAL, "%s", err.c_str());
+        bgp_metrics(p, b);
+    }
     *out = strdup(p.o.str().c_str());
     return 0;
 }
@@ -1551,6 +1585,7 @@ int pv_window_opentelemetry(pv_ctx *c, uint32_t period, uint32_t handlers, const
     *out = nullptr;
     *bytes = 0;
     if (handlers & PV_HANDLER_DHCP) return c->fail(PV_EUNSUPPORTED, "window_opentelemetry: not built for the DHCP handler");
+    if (handlers & PV_HANDLER_BGP) return c->fail(PV_EUNSUPPORTED, "window_opentelemetry: not built for the BGP handler");
     std::lock_guard<std::mutex> g(c->mu); // values drained under the lock (pv_window_json)
     int rc = sync_xvals(c);
     if (rc) return rc;

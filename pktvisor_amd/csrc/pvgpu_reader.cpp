@@ -1,8 +1,12 @@
 // SPDX-License-Identifier: MPL-2.0
 // pvgpu-reader — GPU counterpart of cmd/pktvisor-reader/main.cpp:86-258 for the
-// net + dns handlers: pvgpu-reader [-H HOST_SPEC] [--periods N] [--dhcp] FILE
+// net + dns handlers: pvgpu-reader [-H HOST_SPEC] [--periods N] [--dhcp] [--bgp] FILE
 // Prints {"<N>m": {"packets": {...}, "dns": {...}}} like the reference; --dhcp attaches the
-// DHCP handler too (pktvisor-reader's default) and adds its "dhcp" object.
+// DHCP handler too (pktvisor-reader's default) and adds its "dhcp" object, --bgp the BGP handler
+// and its "bgp" object. With --bgp the file's end also ends the capture (pv_set_end_of_capture:
+// closeAllConnections, as the reference's reader and pktvisor_amd.pktvisor_reader do), which the
+// DNS-over-TCP stage hears too: on a capture that ends with DNS/TCP connections open, "dns" then
+// holds what their flush delivers, where a run without the flag leaves them open as before.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,12 +21,13 @@ int main(int argc, char **argv)
 {
     std::string host, file;
     unsigned periods = 5;
-    bool dhcp = false;
+    bool dhcp = false, bgp = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a == "-H" && i + 1 < argc) host = argv[++i];
         else if (a == "--periods" && i + 1 < argc) periods = (unsigned)atoi(argv[++i]);
         else if (a == "--dhcp") dhcp = true;
+        else if (a == "--bgp") bgp = true;
         else file = a;
     }
     std::ifstream f(file, std::ios::binary);
@@ -48,6 +53,12 @@ int main(int argc, char **argv)
     if (dhcp) {
         pv_dhcp_config dc{};
         if (pv_set_dhcp(ctx, &dc)) { fprintf(stderr, "Fatal error: %s\n", pv_last_error(ctx)); pv_destroy(ctx); return 1; }
+    }
+    if (bgp) {
+        pv_bgp_config bc{};
+        if (pv_set_bgp(ctx, &bc)) { fprintf(stderr, "Fatal error: %s\n", pv_last_error(ctx)); pv_destroy(ctx); return 1; }
+        // the file's end closes the connections still open (PcapInputStream.cpp:522)
+        pv_set_end_of_capture(ctx, 1);
     }
     rc = pv_process_host(ctx, buf.data() + 24, buf.size() - 24);
     if (!rc && nrec) {

@@ -156,6 +156,11 @@ def process_shard(handlers, recs, index, start_sec: int, start_nsec: int = 0, gr
         from pktvisor_amd import PvError
         raise PvError("process_shard failed (-4): the multi-GPU reduce does not carry DHCP state "
                       "(a DHCP handler is attached): process the capture on one rank")
+    if getattr(handlers, "bgp_attached", False):
+        # nor the BGP manager's buckets, open connections and held fragments
+        from pktvisor_amd import PvError
+        raise PvError("process_shard failed (-4): the multi-GPU reduce does not carry BGP state "
+                      "(a BGP handler is attached): process the capture on one rank")
     handlers.set_start_tstamp(start_sec, start_nsec)
     if not getattr(handlers, "slow_defer", False):
         try:

@@ -1,0 +1,422 @@
+"""Python model of the BGP handler (test infrastructure): an independent restatement, from the
+rules, of the segment extraction of pktvisor_amd/csrc/pv_bgp.h, of PcapPlusPlus's TcpReassembly
+and the pcap input's LRU time-outs restricted to port-179 connections, and of BgpMetricsManager /
+BgpMetricsBucket (src/handlers/bgp/BgpStreamHandler.cpp), over classic-pcap records: record walk,
+TCP location (the Net pass's meaning of "a TCP packet"), flow key, reassembly, manager, JSON and
+Prometheus text. Precedent: tests/dhcp_ref.py."""
+import struct
+from collections import OrderedDict
+
+from tests.dhcp_ref import Jsf32, be16, records  # noqa: F401  (the shared generator and record walk)
+
+BGP_PORT = 179
+MAX_OOO = 50
+TIMEOUT = 30
+RECLAIM = 300
+PAY_MAX = 65535
+
+
+def locate_tcp(frame: bytes, linktype: int):
+    """The TCP layer as PcapPlusPlus / the Net pass see it: (l4off, l4len, first IPv4 offset or
+    None, first IPv6 offset or None), or None when the packet has no TCP layer. Offsets are into
+    frame; l4len is trimmed by the IP lengths and the captured bytes."""
+    cur, ln, kind = 0, len(frame), 0
+    if linktype in (1, 113):
+        if linktype == 1:
+            if ln < 14:
+                return None
+            et = be16(frame, 12)
+            if not (et >= 0x600 and ln > 14):
+                return None
+            cur, ln = 14, ln - 14
+        else:
+            if ln <= 16:
+                return None
+            et = be16(frame, 14)
+            cur, ln = 16, ln - 16
+        tags = 0
+        while tags < 8 and et in (0x8100, 0x88A8):
+            if ln <= 4:
+                return None
+            et = be16(frame, cur + 2)
+            cur, ln, tags = cur + 4, ln - 4, tags + 1
+        kind = {0x0800: 4, 0x86DD: 6}.get(et, 0)
+    elif linktype in (101, 12, 14, 228, 229):
+        if ln >= 1 and frame[0] >> 4 in (4, 6):
+            kind = frame[0] >> 4
+    v4 = v6 = None
+    for _ in range(4):
+        if kind == 4:
+            if ln < 20 or frame[cur] >> 4 != 4 or frame[cur] & 15 < 5:
+                return None
+            v4 = cur if v4 is None else v4
+            total = be16(frame, cur + 2)
+            if total and total < ln:
+                ln = total
+            hl = (frame[cur] & 15) * 4
+            if ln <= hl or be16(frame, cur + 6) & 0x3fff:
+                return None
+            proto = frame[cur + 9]
+        elif kind == 6:
+            if ln < 40:
+                return None
+            v6 = cur if v6 is None else v6
+            proto, hl, frag = frame[cur + 6], 40, False
+            for _e in range(8):
+                if not (ln >= 2 and hl <= ln - 2):
+                    break
+                if proto == 44:
+                    step = 8
+                elif proto in (0, 60, 43):
+                    step = (frame[cur + hl + 1] + 1) * 8
+                elif proto == 51:
+                    step = (frame[cur + hl + 1] + 2) * 4
+                else:
+                    break
+                frag = proto == 44
+                proto = frame[cur + hl]
+                hl += step
+            ln = min(ln, be16(frame, cur + 4) + hl)
+            if ln <= hl or frag:
+                return None
+        else:
+            return None
+        pl, pll = cur + hl, ln - hl
+        if proto == 6:
+            return (pl, pll, v4, v6) if pll >= 20 else None
+        if proto in (4, 41) and pll >= 1:
+            kind = frame[pl] >> 4 if frame[pl] >> 4 in (4, 6) else 0
+            cur, ln = pl, pll
+            continue
+        return None
+    return None
+
+
+def fnv1(data: bytes, h: int = 0x811C9DC5) -> int:
+    for b in data:
+        h = ((h * 0x01000193) & 0xFFFFFFFF) ^ b
+    return h
+
+
+def flow_key(frame: bytes, l4off: int, v4, v6) -> int:
+    """PcapPlusPlus hash5Tuple(packet, directionUnique=false): FNV-1 over the two ports, the two
+    addresses (the lower port's side first; equal ports: the lower address's; both compared as
+    little-endian loads of the wire bytes) and the protocol byte. With an IPv4 header anywhere in
+    the packet its first one gives the addresses, else the first IPv6 header."""
+    sp, dp = frame[l4off:l4off + 2], frame[l4off + 2:l4off + 4]
+    lt = lambda a, b: int.from_bytes(a, "little") < int.from_bytes(b, "little")  # noqa: E731
+    swap = lt(dp, sp)
+    if v4 is not None:
+        s, d, proto = frame[v4 + 12:v4 + 16], frame[v4 + 16:v4 + 20], frame[v4 + 9:v4 + 10]
+        if sp == dp and lt(d, s):
+            swap = True
+    else:
+        s, d, proto = frame[v6 + 8:v6 + 24], frame[v6 + 24:v6 + 40], frame[v6 + 6:v6 + 7]
+    if swap:
+        return fnv1(dp + sp + d + s + proto)
+    return fnv1(sp + dp + s + d + proto)
+
+
+def scan_record(rec: bytes, index: int, linktype: int = 1, ts_nano: int = 0):
+    """One pcap record (16-byte header + captured bytes) -> (its second when it is a TCP record,
+    else None; its BGP segment dict, else None)"""
+    sec, frac, cap, _ = struct.unpack_from("<IIII", rec, 0)
+    frame = rec[16:16 + cap]
+    t = locate_tcp(frame, linktype)
+    if t is None:
+        return None, None
+    l4off, l4len, v4, v6 = t
+    sport, dport = be16(frame, l4off), be16(frame, l4off + 2)
+    if BGP_PORT not in (sport, dport):
+        return sec, None
+    hl = (frame[l4off + 12] >> 4) * 4
+    if hl < 20 or hl > l4len:
+        return sec, None
+    flags = frame[l4off + 13] & 7
+    data = bytes(frame[l4off + hl:l4off + l4len])[:PAY_MAX]
+    if not data and not flags:
+        return sec, None
+    v6first = v6 is not None and (v4 is None or v6 < v4)
+    src = bytes(frame[v6 + 8:v6 + 24]) if v6first else bytes(frame[v4 + 12:v4 + 16])
+    return sec, {"rec": index, "sec": sec, "nsec": frac if ts_nano else frac * 1000, "fkey": flow_key(frame, l4off, v4, v6),
+                 "seq": struct.unpack_from(">I", frame, l4off + 4)[0], "data": data, "sport": sport, "dport": dport,
+                 "fin": bool(flags & 1), "syn": bool(flags & 2), "rst": bool(flags & 4), "side": (v6first, src, sport)}
+
+
+def extract(recs: bytes, linktype: int = 1, ts_nano: int = 0):
+    """(segments of the block in record order, each with "tcp_sec_before": the greatest second of
+    the TCP records before it in the block, 0 = none; the block's greatest TCP second)"""
+    out, tmax = [], 0
+    for i, (pos, _s, _f, cap) in enumerate(records(recs)):
+        tsec, seg = scan_record(recs[pos:pos + 16 + cap], i, linktype, ts_nano)
+        if seg is not None:
+            seg["tcp_sec_before"] = tmax
+            out.append(seg)
+        if tsec is not None:
+            tmax = max(tmax, tsec)
+    return out, tmax
+
+
+def _lt(a, b):
+    return ((a - b) & 0xFFFFFFFF) >= 0x80000000
+
+
+COUNTERS = ("events", "deep_samples", "open", "update", "notification", "keepalive", "routerefresh", "total", "filtered")
+TYPES = {1: "open", 2: "update", 3: "notification", 4: "keepalive", 5: "routerefresh"}
+
+
+class Bucket:
+    def __init__(self, sec=0, nsec=0):
+        self.start, self.end = (sec, nsec), (0, 0)
+        self.read_only, self.length = False, 0
+        self.c = {k: 0 for k in COUNTERS}
+
+
+class _Side:
+    def __init__(self, ident):
+        self.ident, self.next, self.done, self.held = ident, 0, False, []  # held: [seq, bytes] in arrival order
+
+
+class _Conn:
+    def __init__(self):
+        self.sides, self.last_side, self.closed_at, self.end = [], None, None, (0, 0)
+
+
+class Manager:
+    """The pcap input's TcpReassembly for port-179 connections feeding BgpMetricsManager"""
+
+    def __init__(self, num_periods=5, deep_sample_rate=100):
+        self.num_periods = num_periods
+        self.rate = deep_sample_rate or 100
+        self.reset()
+
+    def reset(self):
+        self.buckets = [Bucket()]
+        self.rng = Jsf32()
+        self.deep = True
+        self.started = False
+        self.next_shift = 0
+        self.conns = {}
+        self.lru = OrderedDict()  # flow key -> put stamp; the first item is the least recently put
+        self.clock = 0
+        self.tcp_max = 0
+        self.events = []  # (sec, nsec, type, chunk length)
+
+    # ---- window
+    def set_start(self, sec, nsec):
+        if not self.started:
+            self.buckets[0].start, self.next_shift, self.started = (sec, nsec), sec + 60, True
+
+    def set_end(self, sec, nsec):
+        b = self.buckets[0]
+        b.end, b.length, b.read_only = (sec, nsec), sec - b.start[0], True
+
+    def _shift(self, sec, nsec):
+        p = self.buckets[0]
+        p.end, p.length, p.read_only = (sec, nsec), sec - p.start[0], True
+        self.buckets.insert(0, Bucket(sec, nsec))
+        del self.buckets[self.num_periods:]
+        self.next_shift = sec + 60
+
+    def check_period_shift(self, sec, nsec=0):
+        if self.started and self.num_periods > 1 and sec >= self.next_shift:
+            self._shift(sec, nsec)
+
+    def _event(self, stamp, mtype, length):
+        sec, nsec = stamp
+        if self.rate != 100:
+            self.deep = self.rng.next() % 100 < self.rate
+        if self.num_periods > 1 and sec >= self.next_shift:
+            self._shift(sec, nsec)
+        b = self.buckets[0]
+        b.c["events"] += 1
+        b.c["deep_samples"] += 1 if self.deep else 0
+        b.c["total"] += 1
+        b.c[TYPES[mtype]] += 1
+        self.events.append((sec, nsec, mtype, length))
+
+    # ---- reassembly
+    def _put(self, fk, stamp):
+        self.lru.pop(fk, None)
+        self.lru[fk] = stamp
+
+    def _deliver(self, fk, conn, chunk):
+        if len(chunk) >= 19 and chunk[18] in TYPES:
+            self._event(conn.end, chunk[18], len(chunk))
+        self._put(fk, conn.end)
+
+    def _drain(self, fk, conn, side, force):
+        """held fragments that have become deliverable; with `force` (or more than 50 held) the gap in
+        front of the lowest one is declared missing, over and over"""
+        while True:
+            progress = True
+            while progress:
+                progress = False
+                i = 0
+                while i < len(side.held):
+                    seq, data = side.held[i]
+                    if seq == side.next:
+                        del side.held[i]
+                        side.next = (side.next + len(data)) & 0xFFFFFFFF
+                        self._deliver(fk, conn, data)
+                        progress = True
+                    elif _lt(seq, side.next):
+                        del side.held[i]
+                        end = (seq + len(data)) & 0xFFFFFFFF
+                        if _lt(side.next, end):
+                            skip = (side.next - seq) & 0xFFFFFFFF
+                            side.next = end
+                            self._deliver(fk, conn, data[skip:])
+                            progress = True
+                    else:
+                        i += 1
+            if not side.held or (not force and len(side.held) <= MAX_OOO):
+                return
+            k = 0
+            for i in range(1, len(side.held)):
+                if _lt(side.held[i][0], side.held[k][0]):
+                    k = i
+            seq, data = side.held.pop(k)
+            gap = (seq - side.next) & 0xFFFFFFFF
+            side.next = (seq + len(data)) & 0xFFFFFFFF
+            self._deliver(fk, conn, b"[%d bytes missing]" % gap + data)
+
+    def _close(self, fk):
+        conn = self.conns.get(fk)
+        if conn is None or conn.closed_at is not None:
+            return
+        for k in (0, 1):
+            if k < len(conn.sides):
+                self._drain(fk, conn, conn.sides[k], True)
+        self.lru.pop(fk, None)
+        conn.closed_at = self.clock
+        conn.sides = []
+
+    def _fin_rst(self, fk, conn, k, rst):
+        side = conn.sides[k]
+        if side.done:
+            return
+        side.done = True
+        other = conn.sides[1 - k].done if len(conn.sides) == 2 else False
+        if other or rst:
+            self._close(fk)
+        else:
+            self._drain(fk, conn, side, True)
+
+    def _timeouts(self, sec):
+        self.clock = sec
+        while self.lru:
+            fk, stamp = next(iter(self.lru.items()))
+            if sec < stamp[0] + TIMEOUT:
+                break
+            self._close(fk)
+            self.lru.pop(fk, None)
+
+    def _segment(self, s):
+        self.clock = s["sec"]
+        fk, data = s["fkey"], s["data"]
+        now = (s["sec"], s["nsec"] // 1000 * 1000)
+        conn = self.conns.get(fk)
+        if conn is not None and conn.closed_at is not None:
+            if s["sec"] < conn.closed_at + RECLAIM:
+                return
+            conn = None
+        if conn is None:
+            conn = self.conns[fk] = _Conn()
+            self._put(fk, now)
+        elif now > conn.end:
+            conn.end = now
+        idents = [x.ident for x in conn.sides]
+        first = False
+        if s["side"] in idents:
+            k = idents.index(s["side"])
+        elif len(conn.sides) < 2:
+            conn.sides.append(_Side(s["side"]))
+            k, first = len(conn.sides) - 1, True
+        else:
+            return
+        side = conn.sides[k]
+        if side.done:
+            return
+        closing = s["fin"] or s["rst"]
+        if closing and not data:
+            self._fin_rst(fk, conn, k, s["rst"])
+            return
+        if conn.last_side is not None and conn.last_side != k:
+            self._drain(fk, conn, conn.sides[conn.last_side], True)
+        conn.last_side = k
+        seq, n = s["seq"], len(data)
+        if first:
+            side.next = (seq + n + (1 if s["syn"] else 0)) & 0xFFFFFFFF
+            if n:
+                self._deliver(fk, conn, data)
+        elif _lt(seq, side.next):
+            end = (seq + n) & 0xFFFFFFFF
+            if _lt(side.next, end):
+                skip = (side.next - seq) & 0xFFFFFFFF
+                side.next = end
+                self._deliver(fk, conn, data[skip:])
+        elif seq == side.next:
+            if n:
+                side.next = (seq + n + (1 if s["syn"] else 0)) & 0xFFFFFFFF
+                self._deliver(fk, conn, data)
+                self._drain(fk, conn, side, False)
+        elif n:
+            side.held.append([seq, data])
+            if len(side.held) > MAX_OOO:
+                self._drain(fk, conn, side, True)
+        if closing and conn.closed_at is None:
+            self._fin_rst(fk, conn, k, s["rst"])
+
+    def close_all(self):
+        for fk in sorted(k for k, c in self.conns.items() if c.closed_at is None):
+            self._close(fk)
+
+    def open_connections(self):
+        return len(self.lru)
+
+    def known_connections(self):
+        return len(self.conns)
+
+    def feed(self, recs: bytes, linktype: int = 1, ts_nano: int = 0, eoc: bool = False):
+        """one batch: the input's start stamp is its first record's; eoc: the capture's final batch"""
+        rs = records(recs)
+        if not rs:
+            return
+        self.set_start(rs[0][1], rs[0][2] if ts_nano else rs[0][2] * 1000)
+        segs, tmax = extract(recs, linktype, ts_nano)
+        for s in segs:
+            before = max(self.tcp_max, s["tcp_sec_before"])
+            if before:
+                self._timeouts(before)
+            self._segment(s)
+            self._timeouts(s["sec"])
+        self.tcp_max = max(self.tcp_max, tmax)
+        if self.tcp_max:
+            self._timeouts(self.tcp_max)
+            self.conns = {k: c for k, c in self.conns.items() if c.closed_at is None or c.closed_at + RECLAIM > self.tcp_max}
+        if eoc:
+            self.close_all()
+
+    def window(self, period=0, merged=False) -> dict:
+        """the "bgp" object of window_json"""
+        bs = self.buckets[:period] if merged else [self.buckets[period]]
+        return {"period": {"start_ts": min(b.start[0] for b in bs), "length": sum(b.length for b in bs if b.read_only)},
+                "wire_packets": {k: sum(b.c[k] for b in bs) for k in COUNTERS}}
+
+
+def prometheus(win: dict, labels: str = "{}") -> str:
+    """BgpMetricsBucket::to_prometheus of a window() result (no added labels by default)"""
+    help_ = [("events", "Total BGP wire packets events"),
+             ("deep_samples", "Total BGP wire packets that were sampled for deep inspection"),
+             ("open", "Total BGP packets with message type OPEN"), ("update", "Total BGP packets with message type UPDATE"),
+             ("notification", "Total BGP packets with message type NOTIFICATION"),
+             ("keepalive", "Total BGP packets with message type KEEPALIVE"),
+             ("routerefresh", "Total BGP packets with message type ROUTEREFRESH"),
+             ("total", "Total BGP wire packets matching the configured filter(s)"),
+             ("filtered", "Total BGP wire packets seen that did not match the configured filter(s) (if any)")]
+    out = []
+    for k, h in help_:
+        n = "bgp_wire_packets_" + k
+        out.append(f"# HELP {n} {h}\n# TYPE {n} gauge\n{n}{labels} {win['wire_packets'][k]}\n")
+    return "".join(out)
