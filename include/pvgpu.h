@@ -392,7 +392,10 @@ int pv_edge_carry(pv_ctx *ctx, const uint8_t *in, size_t in_bytes, uint8_t **out
  * delivered behind their missing-data markers and the DNS messages that completes are counted at
  * the connection's end time, with the direction the input cached for its last packet
  * (_packet_dir_cache, :399-416). on = 0 disarms it. The flag applies to that call's final batch
- * (pv_process_host cuts its data into batches) and is cleared by the call. */
+ * (pv_process_host cuts its data into batches) and is cleared by the call. A final batch that
+ * holds no record (an empty call, every record dropped by the BPF filter, only a partial record
+ * behind pv_process_host's last batch) flushes all the same, with the time and direction of the
+ * last record processed before it. */
 int pv_set_end_of_capture(pv_ctx *ctx, int on);
 /* Sharded runs, before the merge: what this shard holds that a merge step exchanges.
  * open_queries: the DNS queries it leaves open at its end, before any edge carry (an upper bound:

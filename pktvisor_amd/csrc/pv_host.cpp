@@ -799,7 +799,7 @@ void pv_destroy(pv_ctx *c)
                     c->d_theta, c->d_ctmp, c->d_ctop, c->d_ovf, c->d_ovf2, c->d_iplog32,
                     c->d_ipx_rep, c->d_ipdir, c->d_ipx_cnt, c->d_slow, c->d_ecs, c->d_eecs, c->d_pecs[0], c->d_pecs[1], c->d_lru_ev, c->d_fclose,
                     c->d_xcnt, c->d_xrhdr, c->d_xtot, c->d_xsend, c->d_xrecv, c->d_xp, c->d_bpf, c->d_fwork, c->d_frecs,
-                    c->d_foffs, c->d_fsc, c->d_fscan, c->d_eoc, c->d_eoc_cnt};
+                    c->d_foffs, c->d_fsc, c->d_fscan, c->d_eoc, c->d_eoc_cnt, c->d_last_rec};
     for (void *p : ptrs) if (p) hipFree(p);
     dhcp_free(c);
     bgp_free(c);
@@ -846,6 +846,7 @@ static void tcp_reset(pv_ctx *c)
     c->n_clist = 0;
     c->carry_used = 0;
     c->tcp_active = false;
+    c->last_rec_kept = false;
     c->lru.clear();
     c->lru_at.clear();
     c->lru_hold.clear();
@@ -1309,28 +1310,41 @@ int tcp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, uint64_t
     if (n_seg > c->tseg_cap)
         return c->fail(PV_ECAPACITY, "%u DNS-over-TCP segments in one batch exceed the capacity %u (max_records)", n_seg,
                        c->tseg_cap);
-    const bool eoc = c->eoc_stage && n > 0;
+    // (a final batch without records flushes with the last record an earlier stage kept)
+    const bool eoc = c->eoc_stage && (n > 0 || c->last_rec_kept);
     c->eoc_stage = false;
     if (n_seg == 0 && !c->tcp_active) return 0;
     if (int rc = tcp_alloc(c)) return rc;
     hipError_t e;
-    // bounds of this stage's output: every byte a flow can deliver (payloads, carried bytes,
-    // missing-data texts) lands in at most one message record, reserved at most three times
-    const uint64_t B = seg_bytes + c->carry_used + 32ull * (n_seg + c->carry_used / 8);
-    if (int rc = PV_GROW(c, c->d_marena, c->marena_cap, 3 * B + 44 * (B / 17 + 2ull * n_seg) + 4096 + PV_RECS_PAD, "TCP message arena"))
-        return rc;
-    uint64_t fcap = c->frag_cap;
-    if (int rc = PV_GROW(c, c->d_frags, fcap, n_seg + c->carry_used / 8 + 64, "TCP fragment pool")) return rc;
-    c->frag_cap = (uint32_t)std::min<uint64_t>(fcap, 0xffffffffull);
     const uint32_t out = c->carry_cur ^ 1;
-    if (int rc = PV_GROW(c, c->d_carry[out], c->carry_cap[out], 2 * B + 8 * (n_seg + c->carry_used / 8) + 4096, "TCP carry arena"))
-        return rc;
+    PvTcpParams &T = *c->h_tparams;
+    // bounds of this stage's output for nseg segments: every byte a flow can deliver (payloads,
+    // carried bytes, missing-data texts) lands in at most one message record, reserved at most three
+    // times. Sized again (the buffers hold nothing yet) when the LRU replay's closes or the end of
+    // the capture add segments to the batch's own.
+    auto size_out = [&](uint64_t nseg) -> int {
+        const uint64_t B = seg_bytes + c->carry_used + 32ull * (nseg + c->carry_used / 8);
+        if (int rc = PV_GROW(c, c->d_marena, c->marena_cap, 3 * B + 44 * (B / 17 + 2ull * nseg) + 4096 + PV_RECS_PAD, "TCP message arena"))
+            return rc;
+        uint64_t fcap = c->frag_cap;
+        if (int rc = PV_GROW(c, c->d_frags, fcap, nseg + c->carry_used / 8 + 64, "TCP fragment pool")) return rc;
+        c->frag_cap = (uint32_t)std::min<uint64_t>(fcap, 0xffffffffull);
+        if (int rc = PV_GROW(c, c->d_carry[out], c->carry_cap[out], 2 * B + 8 * (nseg + c->carry_used / 8) + 4096, "TCP carry arena"))
+            return rc;
+        T.carry_out = c->d_carry[out];
+        T.carry_cap = c->carry_cap[out];
+        T.frags = c->d_frags;
+        T.frag_cap = c->frag_cap;
+        T.marena = c->d_marena;
+        T.marena_cap = c->marena_cap;
+        return 0;
+    };
     if (!c->d_carry[c->carry_cur]) {
         if (int rc = PV_GROW(c, c->d_carry[c->carry_cur], c->carry_cap[c->carry_cur], 4096, "TCP carry arena")) return rc;
     }
     c->tcp_stage++;
-    PvTcpParams &T = *c->h_tparams;
     memset(&T, 0, sizeof T);
+    if (int rc = size_out(n_seg)) return rc;
     T.seg = c->d_tseg;
     T.skey = c->d_tkey[1];
     T.sval = c->d_tval[1];
@@ -1348,15 +1362,9 @@ int tcp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, uint64_t
     T.n_tiles = (uint32_t)((n + 63) / 64);
     T.ts_nano = c->cfg.ts_nano;
     T.carry_in = c->d_carry[c->carry_cur];
-    T.carry_out = c->d_carry[out];
-    T.carry_cap = c->carry_cap[out];
     T.clist_in = c->d_clist[c->carry_cur];
     T.n_clist_in = c->n_clist;
     T.clist_out = c->d_clist[out];
-    T.frags = c->d_frags;
-    T.frag_cap = c->frag_cap;
-    T.marena = c->d_marena;
-    T.marena_cap = c->marena_cap;
     T.moffs = c->d_moffs;
     T.mq = c->d_tmq;
     T.mq_cap = c->tmsg_cap;
@@ -1388,6 +1396,7 @@ int tcp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, uint64_t
         return 0;
     };
     T.exact = c->tcp_exact_on() ? 1u : 0u;
+    std::vector<uint32_t> fcl; // the exact LRU mode's closes, three words a segment
     if (T.exact && n_seg) {
         // the exact LRU mode: record the segments' LRU events, replay the LRU list on the host,
         // then run the stage with the closes it found (close-only segments behind the batch's)
@@ -1402,22 +1411,24 @@ int tcp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, uint64_t
             !hip_ok(e = hipMemcpyAsync(ev.data(), c->d_lru_ev, ev.size() * 4, hipMemcpyDeviceToHost, st)) ||
             !hip_ok(e = hipStreamSynchronize(st)))
             return c->hipfail(e, "TCP LRU events");
-        std::vector<uint32_t> fclose(3ull * n_seg, PVT_FCLOSE_NONE), extra_fc;
+        fcl.assign(3ull * n_seg, PVT_FCLOSE_NONE);
+        std::vector<uint32_t> extra_fc;
         std::vector<PvTcpSeg> extra;
-        tcp_lru_replay(c, skey, sval, ev, fclose, extra, extra_fc);
+        tcp_lru_replay(c, skey, sval, ev, fcl, extra, extra_fc);
         if (!extra.empty()) {
             if (n_seg + extra.size() > c->tseg_cap)
                 return c->fail(PV_ECAPACITY, "%u TCP segments and %zu LRU closes in one batch exceed the capacity %u (max_records)",
                                n_seg, extra.size(), c->tseg_cap);
-            fclose.insert(fclose.end(), extra_fc.begin(), extra_fc.end());
+            fcl.insert(fcl.end(), extra_fc.begin(), extra_fc.end());
             if (!hip_ok(e = hipMemcpyAsync(c->d_tseg + n_seg, extra.data(), extra.size() * sizeof(PvTcpSeg), hipMemcpyHostToDevice, st)))
                 return c->hipfail(e, "TCP LRU closes");
             n_seg += (uint32_t)extra.size();
             T.n_seg = n_seg;
             blocks = (n_seg + 255) / 256;
+            if (int rc = size_out(n_seg)) return rc;
         }
         if (int rc = PV_GROW(c, c->d_fclose, c->fclose_cap, 3ull * n_seg, "TCP LRU closes")) return rc;
-        if (!hip_ok(e = hipMemcpyAsync(c->d_fclose, fclose.data(), fclose.size() * 4, hipMemcpyHostToDevice, st)))
+        if (!hip_ok(e = hipMemcpyAsync(c->d_fclose, fcl.data(), fcl.size() * 4, hipMemcpyHostToDevice, st)))
             return c->hipfail(e, "TCP LRU closes");
         c->tcp_stage++;
         T.stage = c->tcp_stage;
@@ -1450,16 +1461,22 @@ int tcp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, uint64_t
             !hip_ok(e = hipMemsetAsync(d_set, 0, (size_t)8 << set_log2, st)))
             return c->hipfail(e, "TCP end-of-capture key set");
         uint32_t lo = 0;
-        uint8_t rec[16 + 512];
+        uint8_t rec[16 + PV_LAST_REC_CAP];
         memset(rec, 0, sizeof rec);
-        if (!hip_ok(e = hipMemcpyAsync(&lo, d_offs + (n - 1), 4, hipMemcpyDeviceToHost, st)) || !hip_ok(e = hipStreamSynchronize(st)) ||
-            !hip_ok(e = hipMemcpyAsync(rec, d_recs + lo, 16, hipMemcpyDeviceToHost, st)) || !hip_ok(e = hipStreamSynchronize(st)))
+        // (a final batch without records: the last record an earlier stage kept, pv_tcp_keep_last)
+        if (n == 0) {
+            if (!hip_ok(e = hipMemcpyAsync(rec, c->d_last_rec, sizeof rec, hipMemcpyDeviceToHost, st)) ||
+                !hip_ok(e = hipStreamSynchronize(st)))
+                return c->hipfail(e, "last record");
+        } else if (!hip_ok(e = hipMemcpyAsync(&lo, d_offs + (n - 1), 4, hipMemcpyDeviceToHost, st)) ||
+                   !hip_ok(e = hipStreamSynchronize(st)) ||
+                   !hip_ok(e = hipMemcpyAsync(rec, d_recs + lo, 16, hipMemcpyDeviceToHost, st)) || !hip_ok(e = hipStreamSynchronize(st)))
             return c->hipfail(e, "last record");
         uint32_t hdr[4];
         memcpy(hdr, rec, 16);
-        const uint32_t cap = std::min<uint32_t>(hdr[2], 512);
-        if (cap && (!hip_ok(e = hipMemcpyAsync(rec + 16, d_recs + lo + 16, cap, hipMemcpyDeviceToHost, st)) ||
-                    !hip_ok(e = hipStreamSynchronize(st))))
+        const uint32_t cap = std::min<uint32_t>(hdr[2], PV_LAST_REC_CAP);
+        if (n && cap && (!hip_ok(e = hipMemcpyAsync(rec + 16, d_recs + lo + 16, cap, hipMemcpyDeviceToHost, st)) ||
+                         !hip_ok(e = hipStreamSynchronize(st))))
             return c->hipfail(e, "last record");
         PvParams P;
         params_common(c, P, d_recs, d_offs, n);
@@ -1469,7 +1486,7 @@ int tcp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, uint64_t
         if (!hip_ok(e = hipMemsetAsync(c->d_eoc_cnt, 0, 4, st)) || !hip_ok(e = upload_params(c->d_tparams, c->h_tparams, sizeof T, st)))
             return c->hipfail(e, "TCP end of capture");
         hipLaunchKernelGGL(pv_tcp_eoc, dim3((uint32_t)((ncand + 255) / 256)), dim3(256), 0, st, dT, (const PvTcpSeg *)c->d_tseg, n_seg,
-                           d_set, (uint32_t)((1ull << set_log2) - 1), c->d_eoc, c->d_eoc_cnt, (uint32_t)(n - 1), hdr[0], usec,
+                           d_set, (uint32_t)((1ull << set_log2) - 1), c->d_eoc, c->d_eoc_cnt, (uint32_t)(n ? n - 1 : 0), hdr[0], usec,
                            (uint32_t)o.dir);
         uint32_t ne = 0;
         if (!hip_ok(e = hipGetLastError()) || !hip_ok(e = hipMemcpyAsync(&ne, c->d_eoc_cnt, 4, hipMemcpyDeviceToHost, st)) ||
@@ -1480,14 +1497,17 @@ int tcp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, uint64_t
             if (!hip_ok(e = hipMemcpyAsync(c->d_tseg + n_seg, c->d_eoc, (size_t)ne * sizeof(PvTcpSeg), hipMemcpyDeviceToDevice, st)))
                 return c->hipfail(e, "TCP end of capture");
             if (T.fclose) {
-                // (the exact LRU mode's closes are per segment: none for these)
-                std::vector<uint32_t> none(3ull * ne, PVT_FCLOSE_NONE);
-                if (int rc = PV_GROW(c, c->d_fclose, c->fclose_cap, 3ull * (n_seg + ne), "TCP LRU closes")) return rc;
-                if (!hip_ok(e = hipMemcpyAsync(c->d_fclose + 3ull * n_seg, none.data(), none.size() * 4, hipMemcpyHostToDevice, st)) ||
+                // the exact LRU mode's closes are per segment: none for these. A grow keeps nothing,
+                // so the replay's closes of the batch's own segments go up again with them.
+                fcl.resize(3ull * ((uint64_t)n_seg + ne), PVT_FCLOSE_NONE);
+                if (int rc = PV_GROW(c, c->d_fclose, c->fclose_cap, fcl.size(), "TCP LRU closes")) return rc;
+                if (!hip_ok(e = hipMemcpyAsync(c->d_fclose, fcl.data(), fcl.size() * 4, hipMemcpyHostToDevice, st)) ||
                     !hip_ok(e = hipStreamSynchronize(st)))
                     return c->hipfail(e, "TCP end of capture");
                 T.fclose = c->d_fclose;
             }
+            // (ne is known before the final run: its outputs are sized for the flush segments too)
+            if (int rc = size_out((uint64_t)n_seg + ne)) return rc;
             n_seg += ne;
             T.n_seg = n_seg;
             T.seg = c->d_tseg;
@@ -1498,6 +1518,13 @@ int tcp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, uint64_t
         }
     }
     if (int rc = run(false)) return rc;
+    if (n) {
+        // the batch's last record stays on the device for a flush behind a later batch without
+        // records (no read-back and no synchronisation here)
+        if (!c->d_last_rec && !hip_ok(e = hipMalloc(&c->d_last_rec, 16 + PV_LAST_REC_CAP))) return c->hipfail(e, "last record");
+        hipLaunchKernelGGL(pv_tcp_keep_last, dim3(1), dim3(256), 0, st, d_recs, d_offs, (uint32_t)n, c->d_last_rec);
+        c->last_rec_kept = true;
+    }
     if (!hip_ok(e = hipMemcpyAsync(c->h_tcpcnt, c->d_tcpcnt, PVT_WORDS * 4, hipMemcpyDeviceToHost, st)) ||
         !hip_ok(e = hipStreamSynchronize(st)))
         return c->hipfail(e, "TCP stage");
@@ -2068,6 +2095,10 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
 {
     const uint32_t np = c->cfg.num_periods;
     const uint32_t *d_offs = d_boffs + a;
+    // n == 0: the span of an end-of-capture flush behind a batch without records (flush_empty). No
+    // record kernel runs; the flush's messages, ranked at a record 0, go through the TCP DNS pass
+    // and the transaction stage as any span's do.
+    const uint64_t nord = n ? n : 1;
     PvParams P;
     params_common(c, P, d_recs, d_offs, n);
     // a batch with no TCP stage ahead of it is one span: its Net pass emits the TCP segments
@@ -2106,7 +2137,8 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
                 return c->hipfail(e, "deep sampling filter bits");
         }
         uint32_t tseg[2];
-        if (int rc = dns_prescan(c, d_recs, d_offs, n, st, false, tseg, filt)) return rc;
+        if (n)
+            if (int rc = dns_prescan(c, d_recs, d_offs, n, st, false, tseg, filt)) return rc;
         // the span's messages (ord in [4a, 4(a + n))), and which of them are filtered
         const uint32_t nmsg = c->tcp_nmsg;
         if (nmsg) {
@@ -2121,7 +2153,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
             if (!filtered) c->dns_deep_now = c->draws_dns.next(c->sample_rate);
             return c->dns_deep_now;
         };
-        const uint64_t olo = a * 4, ohi = (a + n) * 4;
+        const uint64_t olo = a * 4, ohi = (a + nord) * 4;
         auto it = std::lower_bound(c->tcp_items.begin(), c->tcp_items.end(), std::make_pair(olo, 0u));
         c->draws_net.take_not_deep(c->sample_rate, hn, n);
         // the DNS events in stream order: each DNS-port UDP record, then the messages a TCP
@@ -2144,7 +2176,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
                 if (!dns_draw(f)) hd[i >> 5] |= 1u << (i & 31);
             }
         }
-        tcp_upto(n);
+        tcp_upto(nord);
         if (!hip_ok(e = hipMemcpyAsync(c->d_ndeep, c->h_ndeep, words * 8, hipMemcpyHostToDevice, st)) ||
             (nmsg && !hip_ok(e = hipMemcpyAsync(c->d_ntcp, c->h_ntcp, ((size_t)nmsg / 32 + 1) * 4, hipMemcpyHostToDevice, st))))
             return c->hipfail(e, "deep sampling bitmaps");
@@ -2197,7 +2229,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     P.flags = c->d_status + ST_FLAGS;
     launch_fill32(c, c->d_status, ST_ALLOC, 0);
     hipError_t e;
-    const uint64_t tiles = (n + 63) / 64; // 64-record wave tiles
+    const uint64_t tiles = (nord + 63) / 64; // 64-record wave tiles
     // persistent grid: exactly the workgroups that are resident at once (LDS/VGPR
     // occupancy), each owning a contiguous run of wave tiles
     // (a batch after one that was mostly DNS messages takes four ranges per CU: the DNS pass,
@@ -2373,11 +2405,11 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     const PvParams *dp = (const PvParams *)c->d_params;
     // (stamping a dispatch costs ~14 us of idle around it: only the batches pv_set_kernel_timing
     // asks for are stamped)
-    const bool timed = c->timing_every && (c->timing_ctr++ % c->timing_every) == 0;
+    const bool timed = n && c->timing_every && (c->timing_ctr++ % c->timing_every) == 0;
     hipEvent_t e0 = timed ? c->ev_start : nullptr, e1 = timed ? c->ev_stop : nullptr;
     // (the stamps bracket the Net pass alone: a stamped batch is not fused)
     if (timed) fuse = false;
-    if (P.gfilt) {
+    if (P.gfilt && n) {
         // the geo filters' verdict of every record of the span, for the general pass to read
         PvGeoArgs G{};
         for (int k = 0; k < 2; k++) {
@@ -2393,7 +2425,8 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
                            (const uint8_t *)(c->nf_on[0] ? c->d_nf_pass[0] : nullptr),
                            (const uint8_t *)(c->nf_on[1] ? c->d_nf_pass[1] : nullptr), c->d_gfilt);
     }
-    if (general) hipExtLaunchKernelGGL(pv_net_kernel, dim3(grid), dim3(PV_NET_THREADS), 0, st, e0, e1, 0, dp);
+    if (!n) { /* no record: the status words' reset above is all the chain leaves */ }
+    else if (general) hipExtLaunchKernelGGL(pv_net_kernel, dim3(grid), dim3(PV_NET_THREADS), 0, st, e0, e1, 0, dp);
     else if (lean) {
         // the lean pass, then its deferred general-path records (the dispatch stamps span both; on
         // the short chain, which has no second launch, both stamps are the lean pass's)
@@ -2469,7 +2502,9 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         memcpy(status, c->h_status, sizeof status);
         return hipSuccess;
     };
-    if (!plain) {
+    if (!n) {
+        // (read_status below then reads the reset words: no event, no key)
+    } else if (!plain) {
         dns_stage();
         topn_stage();
         names_stage();
@@ -2507,8 +2542,10 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         names_stage();
         if (!hip_ok(e = read_status())) return c->hipfail(e, "kernel execution");
     }
-    c->dns_heavy = (uint64_t)status[ST_NDNS] * 2 > n;
-    c->cb_plain = lean && status[ST_NDNS] == 0 && status[ST_NSLOW] == 0;
+    if (n) {
+        c->dns_heavy = (uint64_t)status[ST_NDNS] * 2 > n;
+        c->cb_plain = lean && status[ST_NDNS] == 0 && status[ST_NSLOW] == 0;
+    }
     if (status[ST_FLAGS] & PVF_NAMES_PENDING) {
         // more created entries than the new-name list holds: their names, before anything reads
         // or purges the tables
@@ -2528,7 +2565,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     if (!c->tcp_pre) {
         if (int rc = tcp_stage(c, d_recs, d_offs, n, status[ST_TSEG], status[ST_TSEG_BYTES], first_sec, false, st)) return rc;
     }
-    const uint32_t gt = tcp_pass(c, P, a, a + n, st, c->h_params + 1);
+    const uint32_t gt = tcp_pass(c, P, a, a + nord, st, c->h_params + 1);
     if (gt) {
         // the TCP messages' events behind the UDP pass's key list
         if (P.want_events)
@@ -2678,6 +2715,35 @@ int batch_shifts(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, const
     }
     if (dns_may) dns_shifts_of(c->dns.next_shift_sec, c->h_dbits, info->n_records, info, sc_idx, sc_sec, c->tcp_ords, dsh);
     return 0;
+}
+
+// The end-of-capture flush of a final batch without records (none in the call, none left by the
+// BPF filter, or only a partial record behind pv_process_host's last batch): the reference closes
+// every connection when the file ends, whatever its last packets were (PcapInputStream.cpp:522).
+// The BGP handler's connections close; the TCP stage runs on the close segments alone, with the
+// time and direction of the last record a stage saw (pv_tcp_keep_last), and the messages it
+// delivers take a span of their own, without records. The caller holds c->mu.
+int flush_empty(pv_ctx *c, hipStream_t st)
+{
+    if (c->bgp) c->bgp->close_all();
+    if (!c->tcp_active || !c->last_rec_kept) return 0;
+    c->tcp_pre = true;
+    c->tcp_nmsg = 0;
+    c->tcp_ords.clear();
+    c->tcp_items.clear();
+    c->eoc_stage = true;
+    if (int rc = tcp_stage(c, nullptr, nullptr, 0, 0, 0, (uint32_t)c->last_sec, true, st)) return rc;
+    if (!c->tcp_nmsg) return 0;
+    std::vector<Shift> nsh, dsh;
+    if (c->cfg.num_periods > 1) {
+        // a flushed message's stamp (its connection's end time) may shift the DNS manager's period
+        pv_index_info none;
+        memset(&none, 0, sizeof none);
+        dns_shifts_of(c->dns.next_shift_sec, nullptr, 0, &none, nullptr, nullptr, c->tcp_ords, dsh);
+        if (dsh.size() > PV_MAX_SHIFTS)
+            return c->fail(PV_ECAPACITY, "end-of-capture flush: %zu DNS period shifts in one span", dsh.size());
+    }
+    return process_span(c, nullptr, nullptr, 0, 0, 0, nsh, dsh, (uint32_t)c->last_sec, st);
 }
 
 } // namespace
@@ -3067,7 +3133,9 @@ int pv_process_device(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, 
             if (!c->in_host) c->eoc_armed = c->eoc_batch = false;
         }
     } eoc_done{c};
-    if (info->n_records == 0) return 0;
+    if (c->eoc_batch) c->eoc_ran = true;
+    // (a final batch without records still ends the capture)
+    if (info->n_records == 0) return c->eoc_batch ? flush_empty(c, st) : 0;
     if (info->n_records > c->max_records) return c->fail(PV_ECAPACITY, "batch of %llu records exceeds max_records %llu",
                                            (unsigned long long)info->n_records, (unsigned long long)c->max_records);
     pv_index_info finfo;
@@ -3076,7 +3144,7 @@ int pv_process_device(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, 
         // the pcap input's BPF filter (PcapInputStream.cpp:485-488) over the batch in HBM: the kept
         // records become the batch
         if (int rc = bpf_filter_device(c, d_recs, d_offs, info, st, finfo, fsci, fscs)) return rc;
-        if (finfo.n_records == 0) return 0;
+        if (finfo.n_records == 0) return c->eoc_batch ? flush_empty(c, st) : 0;
         d_recs = c->d_frecs;
         d_offs = c->d_foffs;
         info = &finfo;
@@ -3981,11 +4049,18 @@ int pv_process_host(pv_ctx *c, const uint8_t *recs, size_t bytes)
         std::lock_guard<std::mutex> g(c->mu);
         if (int rc = merged_refuse(c)) return rc;
         c->in_host = true;
+        c->eoc_ran = false;
     }
     // (the pcap input's BPF filter, PcapInputStream.cpp:485-488, runs on the device on each batch:
     // pv_process_device)
-    const int rc = process_host_block(c, recs, bytes);
+    int rc = process_host_block(c, recs, bytes);
     std::lock_guard<std::mutex> g(c->mu);
+    if (!rc && c->eoc_armed && !c->eoc_ran) {
+        // no batch was the final one: the call held no record, or only a partial one behind its
+        // last batch
+        hipSetDevice(c->device);
+        rc = flush_empty(c, c->stream);
+    }
     c->in_host = false;
     c->eoc_armed = c->eoc_batch = c->eoc_stage = false;
     return rc;

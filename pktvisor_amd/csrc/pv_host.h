@@ -235,6 +235,7 @@ extern "C" __global__ void pv_tcp_flow(const PvTcpParams *T);
 extern "C" __global__ void pv_tcp_migrate(const PvTcpParams *T);
 extern "C" __global__ void pv_tcp_eoc(const PvTcpParams *T, const PvTcpSeg *seg, uint32_t n_seg, uint64_t *set, uint32_t set_mask,
                                       PvTcpSeg *out, uint32_t *cnt, uint32_t idx, uint32_t sec, uint32_t usec, uint32_t dir);
+extern "C" __global__ void pv_tcp_keep_last(const uint8_t *recs, const uint32_t *offs, uint32_t n, uint8_t *out);
 extern "C" hipError_t pv_tcp_sort(void *tmp, size_t *tmp_bytes, uint64_t *kin, uint64_t *kout, uint32_t *vin, uint32_t *vout,
                                   size_t n, hipStream_t s);
 
@@ -866,6 +867,13 @@ struct pv_ctx {
     // marks its final batch (eoc_batch) and that batch's last TCP stage (eoc_stage); in_host: inside
     // pv_process_host, whose ingest loops mark the final batch themselves
     bool eoc_armed = false, eoc_batch = false, eoc_stage = false, in_host = false;
+    // eoc_ran: a batch of this pv_process_host call was marked final. A final batch without records
+    // (none left by the filter, an empty call, only a partial record behind the last batch) still
+    // flushes: the TCP stage then runs on the close segments alone, with the time and direction of
+    // the last record a stage saw, which every stage leaves in d_last_rec (its header and up to 512
+    // captured bytes; no read-back until such a flush needs it)
+    bool eoc_ran = false, last_rec_kept = false;
+    uint8_t *d_last_rec = nullptr;
     PvTcpSeg *d_eoc = nullptr; // close segments of the open connections (eoc_cap: flow table + batch segments)
     uint64_t eoc_cap = 0;
     uint32_t *d_eoc_cnt = nullptr;

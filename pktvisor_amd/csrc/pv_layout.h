@@ -642,6 +642,7 @@ enum { PVT_NMSG = 0, PVT_ARENA, PVT_CARRY, PVT_NCARRY, PVT_NFRAG, PVT_FLAGS, PVT
 // the connection holds a fragment that closing it would deliver (the close's own put)
 enum { PVT_EV_NEW = 1, PVT_EV_PUT = 2, PVT_EV_CLOSE = 4, PVT_EV_TIMEOUT = 8, PVT_EV_HOLD = 16 };
 #define PVT_FCLOSE_NONE 0xffffffffu
+#define PV_LAST_REC_CAP 512 // captured bytes of the last record kept for the direction parse (pv_tcp_keep_last)
 enum { PVT_F_TABLE = 1, PVT_F_ARENA = 2, PVT_F_CARRY = 4, PVT_F_FRAGS = 8, PVT_F_MSGS = 16 };
 
 // Device record index of an ingest chunk (pv_index.hip)

@@ -35,7 +35,8 @@
 // tail, and when more than 100 connections time out at one packet. Not modelled in either: the
 // closed-connection purge (wall clock in PcapPlusPlus), the puts of data that closing an evicted
 // connection flushes. The flush of open connections at the end of a capture is pv_tcp_eoc's
-// segments in the final batch (pv_set_end_of_capture).
+// segments in the final batch (pv_set_end_of_capture); a final batch without records runs them
+// alone, with the time and direction of the last record pv_tcp_keep_last kept.
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -676,6 +677,17 @@ extern "C" __global__ void pv_tcp_eoc(const PvTcpParams *__restrict__ Tp, const 
     g.flags = PV_TF_CLOSE | PV_TF_EOC;
     g.dirv6 = (uint8_t)dir;
     out[atomicAdd(cnt, 1u)] = g;
+}
+
+// The batch's last record, its 16-byte header and up to PV_LAST_REC_CAP captured bytes, into out
+// (16 + PV_LAST_REC_CAP bytes): what an end-of-capture flush behind a later batch without records
+// takes its time and direction from. One workgroup; n >= 1.
+extern "C" __global__ void pv_tcp_keep_last(const uint8_t *__restrict__ recs, const uint32_t *__restrict__ offs, uint32_t n,
+                                            uint8_t *__restrict__ out)
+{
+    const uint8_t *r = recs + offs[n - 1];
+    const uint32_t len = 16u + min(rd32(r + 8), (uint32_t)PV_LAST_REC_CAP);
+    for (uint32_t k = threadIdx.x; k < len; k += blockDim.x) out[k] = r[k];
 }
 
 // flows that carried bytes into this batch but had no packet in it keep them: copied to

@@ -248,9 +248,12 @@ def merge_edges(handlers, group=None, comm=None, hints=None):
 
 
 def _no_values(handlers):
-    """every rank reported no DNS transaction value at check_aligned (nothing to select)"""
+    """every rank reported no DNS transaction value at check_aligned, and no open query either
+    (nothing to select). The hints predate merge_edges, which pairs the open queries with the later
+    shards' responses and so creates values: an open query anywhere means values may exist. Every
+    rank holds the same gathered hints, so every rank takes the same branch."""
     hints = getattr(handlers, "_merge_hints", None)
-    return hints is not None and not any(h[1] for h in hints)
+    return hints is not None and not any(h[0] or h[1] for h in hints)
 
 
 def merge_slow(handlers, group=None, comm=None):

@@ -359,6 +359,74 @@ def tcp_reput_pcap() -> bytes:
     return _pcap_of(ev)
 
 
+def _hole18_events(t, cli, cport, name, step=0.1, with_tail=True):
+    """One connection whose server side loses 18 bytes for good: client SYN (sequence 100), server
+    SYN|ACK (900), the framed response up to 30 bytes before its end (901), then, 18 bytes on, its
+    last 12 bytes. The hole lies in the answer records and PcapPlusPlus's "[18 bytes missing]" text
+    is itself 18 bytes, so once the connection closes the framing survives and the question parses;
+    until then the tail is held out of order and no message is delivered."""
+    import struct
+    srv = bytes([8, 8, 8, 8])
+    r = _dns_msg(np.random.default_rng(0), 0x1234, True, name, 1, rcode=0, answers=3)
+    framed = struct.pack(">H", len(r)) + r
+    k = len(framed) - 30
+    ev = [(t, _frame(cli, srv, cport, 53, 100, 0x02, b"", False)),
+          (t + step, _frame(srv, cli, 53, cport, 900, 0x12, b"", False)),
+          (t + 2 * step, _frame(srv, cli, 53, cport, 901, 0x18, framed[:k], False))]
+    if with_tail:
+        ev.append((t + 3 * step, _frame(srv, cli, 53, cport, 901 + k + 18, 0x18, framed[k + 18:], False)))
+    return ev
+
+
+def tcp_hole18_pcap(with_tail: bool = True, noise: int = 0) -> bytes:
+    """The hole-18 connection (_hole18_events) of client 10.0.0.1:40000 alone, within one second:
+    its response is delivered by the end-of-capture flush (closeAllConnections) and by nothing
+    else; without the tail nothing is delivered at all. `noise` appends that many TCP records to
+    port 9999 with 300-byte payloads, one second later (a wire length above 200)."""
+    ev = _hole18_events(0.0, bytes([10, 0, 0, 1]), 40000, "held.example.com", 0.1, with_tail)
+    for j in range(noise):
+        ev.append((1.3 + j * 0.001, _frame(bytes([10, 0, 0, 2]), bytes([9, 9, 9, 9]), 50000, 9999, 5000 + 300 * j, 0x18,
+                                           bytes(300), False)))
+    return _pcap_of(ev)
+
+
+def tcp_many_open_pcap(n_open: int = 26000, late_s: float = 40.0) -> bytes:
+    """Many connections still open when the capture ends. `n_open` clients 10.x.y.z, spread evenly
+    over 20 s, each send a SYN (sequence 1000) and the first 10 bytes of a framed query (1001): held
+    message bytes. Every 400th connection is a hole-18 exchange instead (_hole18_events, a name per
+    connection), whose response only a close delivers. At `late_s` eight fresh connections send a
+    SYN and one complete framed query each, 1 ms apart; after the first of them the four oldest
+    open query connections send the rest of their query. At 40 s PcapInputStream's cleanup (at
+    most 100 connections a packet, 30 s idle) has closed those four by then, so their bytes belong
+    to closed flows; at 25 s nothing is idle and the four queries count."""
+    import struct
+    srv = bytes([8, 8, 8, 8])
+    rng = np.random.default_rng(0)
+    ev = []
+    first_plain = []
+    for i in range(n_open):
+        t = 20.0 * i / n_open
+        cli = bytes([10, (i >> 16) & 255, (i >> 8) & 255, i & 255])
+        if i % 400 == 0:
+            ev += _hole18_events(t, cli, 40000, f"held{i}.example.com", 0.0001)
+            continue
+        q = _dns_msg(rng, i & 0xffff, False, f"open{i % 97}.example.com", 1)
+        framed = struct.pack(">H", len(q)) + q
+        ev.append((t, _frame(cli, srv, 40000, 53, 1000, 0x02, b"", False)))
+        ev.append((t + 0.0002, _frame(cli, srv, 40000, 53, 1001, 0x18, framed[:10], False)))
+        if len(first_plain) < 4:
+            first_plain.append((cli, framed))
+    for k in range(8):
+        cli = bytes([10, 200, 0, k + 1])
+        q = _dns_msg(rng, 0x4000 + k, False, f"final{k}.example.com", 1)
+        t = late_s + 0.001 * k
+        ev.append((t, _frame(cli, srv, 41000, 53, 7000, 0x02, b"", False)))
+        ev.append((t + 0.0002, _frame(cli, srv, 41000, 53, 7001, 0x18, struct.pack(">H", len(q)) + q, False)))
+    for j, (cli, framed) in enumerate(first_plain):
+        ev.append((late_s + 0.0004 + 0.0001 * j, _frame(cli, srv, 40000, 53, 1011, 0x18, framed[10:], False)))
+    return _pcap_of(ev)
+
+
 def tcp_held_evict_pcap(seed: int = 1, flows: int = 48, duration_s: float = 12.0) -> bytes:
     """DNS-over-TCP connections that hold out-of-order fragments for a long time while many
     others start: each client sends its framed queries cut into 3-6 segments, the second one
@@ -402,6 +470,28 @@ def tcp_held_evict_pcap(seed: int = 1, flows: int = 48, duration_s: float = 12.0
         t += float(rng.exponential(0.05))
         ev.append((t, _frame(cli, srv, cp, 53, cs + 1 + len(cb), 0x11, b"", False)))
         ev.append((t + 0.01, _frame(srv, cli, 53, cp, ss + 1 + len(sb), 0x11, b"", False)))
+    return _pcap_of(ev)
+
+
+def _udp_frame(src, dst, sport, dport, payload):
+    """Ethernet + IPv4 + UDP carrying payload"""
+    import struct
+    udp = struct.pack(">HHHH", sport, dport, 8 + len(payload), 0) + payload
+    ip = struct.pack(">BBHHHBBH", 0x45, 0, 20 + len(udp), 0, 0, 64, 17, 0) + src + dst
+    return b"\x00\x11\x22\x33\x44\x55\x66\x77\x88\x99\xaa\xbb\x08\x00" + ip + udp
+
+
+def split_xact_pcap(filler: int = 200) -> bytes:
+    """One DNS transaction and nothing else of DNS: a UDP query in the first record, its response
+    in the last, `filler` UDP records to port 9999 between them (10 ms apart, 64-byte payloads). A
+    capture cut into shards anywhere leaves the query and the response in different shards, so no
+    shard pairs a transaction of its own."""
+    cli, srv = bytes([10, 0, 0, 1]), bytes([8, 8, 8, 8])
+    rng = np.random.default_rng(0)
+    ev = [(0.0, _udp_frame(cli, srv, 40000, 53, _dns_msg(rng, 0x2222, False, "split.example.com", 1)))]
+    for k in range(filler):
+        ev.append((0.01 * (k + 1), _udp_frame(bytes([10, 0, 1, 1 + k % 200]), bytes([9, 9, 9, 9]), 50000 + k, 9999, bytes(64))))
+    ev.append((0.01 * (filler + 1), _udp_frame(srv, cli, 53, 40000, _dns_msg(rng, 0x2222, True, "split.example.com", 1, 0, 2))))
     return _pcap_of(ev)
 
 

@@ -382,6 +382,9 @@ class Manager:
         """one batch: the input's start stamp is its first record's; eoc: the capture's final batch"""
         rs = records(recs)
         if not rs:
+            # (closeAllConnections runs at the end of the file whatever the final batch holds)
+            if eoc:
+                self.close_all()
             return
         self.set_start(rs[0][1], rs[0][2] if ts_nano else rs[0][2] * 1000)
         segs, tmax = extract(recs, linktype, ts_nano)

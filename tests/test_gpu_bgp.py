@@ -266,6 +266,31 @@ def test_end_of_capture_flush():
     assert check([recs[:len(syn)], recs[len(syn):]], eoc=True)["wire_packets"]["notification"] == 1
 
 
+def test_end_of_capture_flush_empty_final_batch():
+    """the flush stream with bpf=DROP_443: the armed final batch is one record that the filter
+    drops, so no record of it reaches the handler; the connections close all the same (the
+    reference's closeAllConnections runs at the end of the file whatever the filter kept) and the
+    held NOTIFICATION is delivered. The model: the kept records, then an empty final feed."""
+    a, _b, syn = bc.opened()
+    recs = syn + a.send(bc.bgp_msg(1), T0, 2)
+    a.skip(1)
+    recs += a.send(bytes([0, 3]) + bytes(20), T0, 3)
+    tail = bc.foreign(T0, 4)
+    assert pa.bpf_filter(recs, DROP_443) == recs and pa.bpf_filter(tail, DROP_443) == b""
+    h = pa.PvHandlers(max_records=n_records(recs), bgp_config={}, bpf=DROP_443)
+    m = bgp_ref.Manager()
+    try:
+        h.process_host(recs)
+        m.feed(recs)
+        assert h.window_json()["bgp"] == m.window() and m.window()["wire_packets"]["notification"] == 0
+        h.set_end_of_capture()
+        h.process_host(tail)
+        m.feed(b"", eoc=True)
+        assert h.window_json()["bgp"] == m.window() and m.window()["wire_packets"]["notification"] == 1
+    finally:
+        h.close()
+
+
 def test_device_resident_batch():
     """pv_process_device directly (no ingest in front): the stage hooks there"""
     import numpy as np
