@@ -2586,6 +2586,37 @@ int pvo_jsf32(uint32_t n, uint32_t *out)
     return 0;
 }
 
+// parse_packet + set_direction over a blob of classic-pcap records (16-byte header + caplen bytes
+// each), ten values a record: l3, l4, has4, has6, syn, dir, then the offsets of the first IPv4
+// header, the first IPv6 header and the L4 header from frame byte 0 (-1 where absent), and the
+// L4 layer length. Returns the rows written, or -1 for a host spec that does not parse.
+int64_t pvo_parse_packets(const uint8_t *blob, uint64_t len, uint32_t linktype, const char *host_spec, int64_t *rows,
+                          uint64_t max_rows)
+{
+    using namespace pvo;
+    Config c;
+    std::string err;
+    if (!parse_host_specs(host_spec ? host_spec : "", c, err)) return -1;
+    uint64_t pos = 0, n = 0;
+    while (pos + 16 <= len && n < max_rows) {
+        const uint32_t cap = rd32le(blob + pos + 8);
+        if (pos + 16 + cap > len) break;
+        Pkt p;
+        p.data = blob + pos + 16;
+        p.caplen = cap;
+        parse_packet(p, linktype);
+        set_direction(p, c);
+        int64_t *r = rows + 10 * n++;
+        r[0] = p.l3; r[1] = p.l4; r[2] = p.has_v4; r[3] = p.has_v6; r[4] = p.syn; r[5] = p.dir;
+        r[6] = p.has_v4 ? p.v4hdr - p.data : -1;
+        r[7] = p.has_v6 ? p.v6hdr - p.data : -1;
+        r[8] = p.l4 != L4_UNKNOWN ? p.l4hdr - p.data : -1;
+        r[9] = p.l4len;
+        pos += 16 + (uint64_t)cap;
+    }
+    return (int64_t)n;
+}
+
 } // extern "C"
 
 #ifdef PVO_MAIN

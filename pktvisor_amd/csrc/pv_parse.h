@@ -290,7 +290,8 @@ PV_FN void parse_record(const A &R, const ParseCfg &C, PV_CREF(PvParams) P, uint
         }
         kind = et == 0x0800 ? 4 : (et == 0x86DD ? 6 : 0);
     }
-    for (int depth = 0; depth < 4 && kind; depth++) {
+    // five IP headers, as the oracle's parse_ip walks (depth 0..4)
+    for (int depth = 0; depth < 5 && kind; depth++) {
         uint32_t proto, hl;
         if (kind == 4) {
             uint32_t b0 = R.u8(cur);
@@ -309,7 +310,8 @@ PV_FN void parse_record(const A &R, const ParseCfg &C, PV_CREF(PvParams) P, uint
             uint32_t next = R.u8(cur + 6);
             uint32_t off = 40;
             bool frag = false;
-            for (int e = 0; e < 8 && len >= 2 && off <= len - 2; e++) {
+            // bounded by the remaining length alone (every step adds at least 8 to off)
+            while (len >= 2 && off <= len - 2) {
                 uint32_t elen;
                 if (next == 44) elen = 8;
                 else if (next == 0 || next == 60 || next == 43) elen = (R.u8(cur + off + 1) + 1) * 8;

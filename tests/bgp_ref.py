@@ -45,7 +45,7 @@ def locate_tcp(frame: bytes, linktype: int):
         if ln >= 1 and frame[0] >> 4 in (4, 6):
             kind = frame[0] >> 4
     v4 = v6 = None
-    for _ in range(4):
+    for _ in range(5):  # five IP headers, as the oracle walks
         if kind == 4:
             if ln < 20 or frame[cur] >> 4 != 4 or frame[cur] & 15 < 5:
                 return None
@@ -62,9 +62,7 @@ def locate_tcp(frame: bytes, linktype: int):
                 return None
             v6 = cur if v6 is None else v6
             proto, hl, frag = frame[cur + 6], 40, False
-            for _e in range(8):
-                if not (ln >= 2 and hl <= ln - 2):
-                    break
+            while ln >= 2 and hl <= ln - 2:  # bounded by the length alone
                 if proto == 44:
                     step = 8
                 elif proto in (0, 60, 43):

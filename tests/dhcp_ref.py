@@ -81,7 +81,7 @@ def locate_udp(frame: bytes, linktype: int):
             v = frame[0] >> 4
             kind = v if v in (4, 6) else 0
     v4 = v6 = None
-    for _ in range(4):
+    for _ in range(5):  # five IP headers, as the oracle walks
         if not kind:
             return None
         if kind == 4:
@@ -107,9 +107,7 @@ def locate_udp(frame: bytes, linktype: int):
             if v6 is None:
                 v6 = cur
             nxt, off, frag = frame[cur + 6], 40, False
-            for _e in range(8):
-                if not (ln >= 2 and off <= ln - 2):
-                    break
+            while ln >= 2 and off <= ln - 2:  # bounded by the length alone
                 if nxt == 44:
                     elen = 8
                 elif nxt in (0, 60, 43):

@@ -83,3 +83,95 @@ int h_name_fast_check(const uint8_t *msg, uint32_t len)
            a.h3 == b.h3;
 }
 }
+
+#include <arpa/inet.h>
+
+// PvParams::nets from subnet lists, as pv_host.cpp fills it from a host spec (v4: in_addr.s_addr
+// and CIDR; v6: 16 address bytes and CIDR)
+static void fill_nets(PvSubnets &s, uint32_t n4, const uint32_t *v4_addr, const uint32_t *v4_cidr, uint32_t n6,
+                      const uint8_t *v6_addr, const uint32_t *v6_cidr)
+{
+    memset(&s, 0, sizeof s);
+    for (uint32_t i = 0; i < n4 && i < PV_MAX_SUBNETS; i++) {
+        const uint32_t k = s.n4++;
+        s.v4_addr[k] = v4_addr[i];
+        s.v4_all[k] = v4_cidr[i] == 0;
+        s.v4_mask[k] = v4_cidr[i] == 0 ? 0 : htonl(0xFFFFFFFFu << (32 - v4_cidr[i]));
+    }
+    for (uint32_t i = 0; i < n6 && i < PV_MAX_SUBNETS; i++) {
+        memcpy(s.v6_addr[s.n6], v6_addr + 16 * i, 16);
+        s.v6_cidr[s.n6++] = v6_cidr[i];
+    }
+}
+
+// one row of PV_PARSE_COLS values per record: l3, l4, has4, has6, syn, dir, v4, v6, l4off, l4len;
+// the three offsets relative to frame byte 0, -1 where the layer is absent
+#define PV_PARSE_COLS 10
+template <class A>
+static void parse_row(const A &R, const PvParams &P, uint64_t rec, int64_t *row)
+{
+    Parsed o;
+    parse_record(R, P, rec, o);
+    row[0] = o.l3; row[1] = o.l4; row[2] = o.has4; row[3] = o.has6; row[4] = o.syn; row[5] = o.dir;
+    row[6] = o.has4 ? (int64_t)(o.v4 - o.frame) : -1;
+    row[7] = o.has6 ? (int64_t)(o.v6 - o.frame) : -1;
+    row[8] = o.l4 ? (int64_t)(o.l4off - o.frame) : -1;
+    row[9] = o.l4len;
+}
+
+extern "C" {
+// parse_record over a blob of classic-pcap records (16-byte header + caplen bytes each; the blob
+// readable 8 bytes past len). Returns the number of rows written (at most max_rows).
+uint64_t h_parse_records(const uint8_t *blob, uint64_t len, uint32_t linktype, uint32_t ts_nano, uint32_t n4,
+                         const uint32_t *v4_addr, const uint32_t *v4_cidr, uint32_t n6, const uint8_t *v6_addr,
+                         const uint32_t *v6_cidr, int64_t *rows, uint64_t max_rows)
+{
+    PvParams P;
+    memset(&P, 0, sizeof P);
+    P.linktype = linktype;
+    P.ts_nano = ts_nano;
+    fill_nets(P.nets, n4, v4_addr, v4_cidr, n6, v6_addr, v6_cidr);
+    const HAcc R{blob};
+    uint64_t pos = 0, n = 0;
+    while (pos + 16 <= len && n < max_rows) {
+        const uint32_t cap = R.u32(pos + 8);
+        if (pos + 16 + cap > len) break;
+        parse_row(R, P, pos, rows + PV_PARSE_COLS * n++);
+        pos += 16 + (uint64_t)cap;
+    }
+    return n;
+}
+}
+
+#ifdef PV_PARSE_BOUNDED
+// Accessor for the stand-alone sanitizer program (parse_asan_main.cpp): the record lives in a heap
+// block of exactly its own size. A byte read goes to memory as it is, so one past the block is a
+// sanitizer report. A word read is how the kernels fetch a 16-bit field (one LDS word, the upper
+// bytes masked off), so it may straddle the end by design: its bytes inside the block are read,
+// those past it are taken from `fill`. The program parses every record under two fills and the two
+// rows must be equal, so a result that depends on a byte past the record is a finding either way.
+struct BAcc {
+    const uint8_t *R;
+    uint64_t end;
+    uint8_t fill;
+    uint32_t u32(uint64_t off) const
+    {
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < 4; k++) v |= (uint32_t)(off + k < end ? R[off + k] : fill) << (8 * k);
+        return v;
+    }
+    uint32_t u32a(uint64_t off) const { return u32(off); }
+    uint32_t u8(uint64_t off) const { return R[off]; }
+};
+extern "C" void h_parse_bounded(const uint8_t *rec, uint64_t size, uint8_t fill, uint32_t linktype, uint32_t n4,
+                                const uint32_t *v4_addr, const uint32_t *v4_cidr, uint32_t n6, const uint8_t *v6_addr,
+                                const uint32_t *v6_cidr, int64_t *row)
+{
+    PvParams P;
+    memset(&P, 0, sizeof P);
+    P.linktype = linktype;
+    fill_nets(P.nets, n4, v4_addr, v4_cidr, n6, v6_addr, v6_cidr);
+    const BAcc R{rec, size, fill};
+    parse_row(R, P, 0, row);
+}
+#endif
