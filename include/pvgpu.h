@@ -628,6 +628,12 @@ int pv_chain_stats(pv_ctx *ctx, uint64_t out[4], int reset);
  * fell back to the regular chain. A choice of speed only; PV_FUSE_PLAIN=0 in the environment
  * (read at every batch) keeps the two launches. */
 int pv_fuse_stats(pv_ctx *ctx, uint64_t out[2], int reset);
+/* Of those, the batches launched without the compact IP log (pv_net_combine_ring: the Net waves
+ * hand each tile's IPv4 words to the inserting waves through LDS; only after two plain batches in a
+ * row) since the last reset: out[0] such batches, out[1] those of them that were not plain after
+ * all, for which pv_net_iplog wrote the log before the regular chain ran. A choice of speed only;
+ * PV_FUSE_RING=0 in the environment (read at every batch) keeps the logged fused launch. */
+int pv_ring_stats(pv_ctx *ctx, uint64_t out[2], int reset);
 
 /* ---- GeoIP / ASN databases (MaxMind DB 2.0), the reference's MaxmindDB (src/GeoDB.h:27-41,
  * src/GeoDB.cpp). A database is parsed from untrusted bytes and compiled at open time: every data

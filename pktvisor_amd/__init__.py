@@ -192,7 +192,8 @@ EXPORTS = ["pv_version", "pv_device_count", "pv_create", "pv_destroy", "pv_last_
            "pv_topn_x_candidates", "pv_topn_x_names", "pv_topn_x_view", "pv_values_x_select", "pv_comm_values_select",
            "pv_slow_x_finish", "pv_comm_slow_finish", "pv_geodb_open", "pv_geodb_open_file", "pv_geodb_close",
            "pv_geodb_last_error", "pv_geodb_entries", "pv_geodb_hash", "pv_geodb_hashes", "pv_set_net_filters", "pv_geodb_entry", "pv_geodb_lookup", "pv_set_geodb",
-           "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing", "pv_set_bgp", "pv_bgp_timing", "pv_chain_stats", "pv_fuse_stats"]
+           "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing", "pv_set_bgp", "pv_bgp_timing", "pv_chain_stats", "pv_fuse_stats",
+           "pv_ring_stats"]
 PV_GEODB_CITY, PV_GEODB_ASN = 0, 1
 # pv_allreduce_fn: (uint64_t *buf, size_t n, int op, void *user) -> int
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
@@ -389,6 +390,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.pv_chain_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.c_int]
     if hasattr(lib, "pv_fuse_stats"):  # (the same)
         lib.pv_fuse_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.c_int]
+    if hasattr(lib, "pv_ring_stats"):  # (the same)
+        lib.pv_ring_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.c_int]
     _lib = lib
     return lib
 
@@ -858,6 +861,13 @@ class PvHandlers:
         the regular chain) since the last reset (pv_fuse_stats)"""
         out = (ctypes.c_uint64 * 2)()
         self._check(self.lib.pv_fuse_stats(self.ctx, out, int(reset)), "pv_fuse_stats")
+        return tuple(int(v) for v in out)
+
+    def ring_stats(self, reset: bool = False):
+        """(fused batches launched without the IP log, of those not plain after all, whose log was rebuilt
+        for the regular chain) since the last reset (pv_ring_stats)"""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self.lib.pv_ring_stats(self.ctx, out, int(reset)), "pv_ring_stats")
         return tuple(int(v) for v in out)
 
     def set_net_filters(self, geoloc_notfound=False, asn_notfound=False, only_geoloc_prefix=None, only_asn_number=None):

@@ -2409,6 +2409,19 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     hipEvent_t e0 = timed ? c->ev_start : nullptr, e1 = timed ? c->ev_stop : nullptr;
     // (the stamps bracket the Net pass alone: a stamped batch is not fused)
     if (timed) fuse = false;
+    // The fused launch without the IP log (pv_net_combine_ring): where every workgroup's group is
+    // compact on these parameters alone, the kernel's `early` condition (the compact table, the lean
+    // pass with top IPs: fuse has them; no group spanning more than 65,535 records; the launch
+    // below has the full workgroup; a last group of a single range, which that condition leaves to
+    // the generic table, runs the compact one there), and only after two plain batches in a row: a
+    // batch that is not plain after all pays for the log's rebuild (pv_net_iplog), so traffic that
+    // alternates between plain and DNS batches never gets here. PV_FUSE_RING=0, read at every
+    // batch, keeps the logged fused launch.
+    bool ring = fuse && P.cb_compact && c->cb_plain_run >= 2 && (uint64_t)P.cb_fan * P.wt_per_block * 64 <= 65535;
+    if (ring) {
+        const char *fr = getenv("PV_FUSE_RING");
+        if (fr && atoi(fr) == 0) ring = false;
+    }
     if (P.gfilt && n) {
         // the geo filters' verdict of every record of the span, for the general pass to read
         PvGeoArgs G{};
@@ -2431,7 +2444,8 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         // the lean pass, then its deferred general-path records (the dispatch stamps span both; on
         // the short chain, which has no second launch, both stamps are the lean pass's)
         hipEvent_t l1 = plain ? e1 : (hipEvent_t) nullptr;
-        if (fuse) hipLaunchKernelGGL(pv_net_combine_plain, dim3(P.cb_grid), dim3(PV_CB_THREADS), 0, st, dp);
+        if (ring) hipLaunchKernelGGL(pv_net_combine_ring, dim3(P.cb_grid), dim3(PV_CB_THREADS), 0, st, dp);
+        else if (fuse) hipLaunchKernelGGL(pv_net_combine_plain, dim3(P.cb_grid), dim3(PV_CB_THREADS), 0, st, dp);
         else if (span) hipExtLaunchKernelGGL(pv_net_kernel_span, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, l1, 0, dp);
         else if (tc) hipExtLaunchKernelGGL(pv_net_kernel_reg_tc, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, l1, 0, dp);
         else hipExtLaunchKernelGGL(pv_net_kernel_reg, dim3(reg_grid), dim3(PV_NET_THREADS), 0, st, e0, l1, 0, dp);
@@ -2513,6 +2527,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         topn_stage(fuse);
         c->chain_n[0]++;
         if (fuse) c->fuse_n[0]++;
+        if (ring) c->nolog_n[0]++;
     }
 
     // ---- transactions: pair responses with queries (sort by key, then record index)
@@ -2530,6 +2545,11 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         P.plain_chain = 0;
         c->h_params->plain_chain = 0;
         if (!hip_ok(e = upload_params(c->d_params, c->h_params, sizeof P, st))) return c->hipfail(e, "parameter upload");
+        if (ring) {
+            // the batch ran without the IP log, which the chain's combine reads for every group
+            c->nolog_n[1]++;
+            hipLaunchKernelGGL(pv_net_iplog, dim3(c->cus * 4), dim3(256), 0, st, dp);
+        }
         hipLaunchKernelGGL(pv_net_slow_list, dim3(c->cus * 2), dim3(256), 0, st, dp);
         dns_stage();
         topn_stage();
@@ -2545,6 +2565,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     if (n) {
         c->dns_heavy = (uint64_t)status[ST_NDNS] * 2 > n;
         c->cb_plain = lean && status[ST_NDNS] == 0 && status[ST_NSLOW] == 0;
+        c->cb_plain_run = c->cb_plain ? std::min(c->cb_plain_run + 1, 2u) : 0;
     }
     if (status[ST_FLAGS] & PVF_NAMES_PENDING) {
         // more created entries than the new-name list holds: their names, before anything reads
@@ -2615,7 +2636,13 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device);
         if (lean && hip_ok(hipMemcpy(nv.data(), c->d_stamps + (1u << 20) + (1u << 18), nv.size() * 8, hipMemcpyDeviceToHost)) && nv[0]) {
             uint64_t first = ~0ull;
-            for (uint32_t w = 0; w < reg_grid; w++) first = std::min(first, nv[w * 4]);
+            // (the start tick's top four bits: the workgroup's XCC id)
+            std::vector<uint32_t> xcc(reg_grid);
+            for (uint32_t w = 0; w < reg_grid; w++) {
+                xcc[w] = (uint32_t)(nv[w * 4] >> 60);
+                nv[w * 4] &= ~(0xfull << 60);
+                first = std::min(first, nv[w * 4]);
+            }
             const double us = khz > 0 ? 1000.0 / khz : 0.01;
             fprintf(stderr, "pv_tstamps net (%u wg, %s):", reg_grid, fuse ? "fused" : "pair");
             static const char *nm[4] = {"start", "net_end", "handover", "end"};
@@ -2626,6 +2653,17 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
                 if (v.empty()) continue;
                 std::sort(v.begin(), v.end());
                 fprintf(stderr, " %s min=%.2f med=%.2f max=%.2f us", nm[k], v.front(), v[v.size() / 2], v.back());
+            }
+            fprintf(stderr, "\n");
+            // the Net phase's end by XCC: does the spread follow the XCDs?
+            fprintf(stderr, "pv_tstamps net_end by xcc:");
+            for (uint32_t x = 0; x < 16; x++) {
+                std::vector<double> v;
+                for (uint32_t w = 0; w < reg_grid; w++)
+                    if (xcc[w] == x && nv[w * 4 + 1]) v.push_back((double)(nv[w * 4 + 1] - first) * us);
+                if (v.empty()) continue;
+                std::sort(v.begin(), v.end());
+                fprintf(stderr, " x%u(n=%zu) %.0f/%.0f/%.0f", x, v.size(), v.front(), v[v.size() / 2], v.back());
             }
             fprintf(stderr, "\n");
             hipMemset(c->d_stamps + (1u << 20) + (1u << 18), 0, nv.size() * 8);
@@ -2970,6 +3008,16 @@ extern "C" int pv_fuse_stats(pv_ctx *c, uint64_t out[2], int reset)
     for (int k = 0; k < 2; k++) {
         if (out) out[k] = c->fuse_n[k];
         if (reset) c->fuse_n[k] = 0;
+    }
+    return 0;
+}
+
+extern "C" int pv_ring_stats(pv_ctx *c, uint64_t out[2], int reset)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int k = 0; k < 2; k++) {
+        if (out) out[k] = c->nolog_n[k];
+        if (reset) c->nolog_n[k] = 0;
     }
     return 0;
 }

@@ -154,6 +154,8 @@ extern "C" __global__ void pv_xact_compact(const PvParams *P, uint32_t b0, uint3
 extern "C" __global__ void pv_dns_prescan(const PvParams *P);
 extern "C" __global__ void pv_topn_combine(const PvParams *P);
 extern "C" __global__ void pv_net_combine_plain(const PvParams *P);
+extern "C" __global__ void pv_net_combine_ring(const PvParams *P);
+extern "C" __global__ void pv_net_iplog(const PvParams *P);
 extern "C" __global__ void pv_topn_combine_r12(const PvParams *P);
 extern "C" __global__ void pv_topn_merge(const PvParams *P);
 extern "C" __global__ void pv_topn_names_sfx(const PvParams *P);
@@ -686,6 +688,8 @@ struct pv_ctx {
     // one, late names launches, batches on the regular chain
     uint64_t chain_n[4] = {0, 0, 0, 0};
     uint64_t fuse_n[2] = {0, 0}; // pv_fuse_stats: short-chain batches launched fused, those that fell back
+    uint32_t cb_plain_run = 0;   // plain batches in a row up to the last one (cb_plain: at least one)
+    uint64_t nolog_n[2] = {0, 0}; // pv_ring_stats: fused batches launched without the IP log, logs rebuilt
     int dns_wg_per_cu = 1; // resident workgroups per CU of the DNS pass (its register count)
     const char *net_kernel = "none"; // the Net-pass kernel the last span launched (pv_net_kernel_name)
     uint64_t *d_dq = nullptr; // DNS work lists (32-B messages)

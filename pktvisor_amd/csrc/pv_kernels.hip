@@ -92,6 +92,7 @@ __device__ __forceinline__ uint32_t pv_alignbyte(uint32_t hi, uint32_t lo, uint3
 // kernel parameters are read through the constant address space (scalar loads)
 #define PV_CREF(T) const PV_C T &
 #include "pv_parse.h"
+#include "pv_ring.h"
 #include <type_traits>
 
 namespace {
@@ -2132,7 +2133,11 @@ __device__ __forceinline__ void win_words(const uint4 (&W)[5], uint32_t sh, RecW
 // and the kernel's last), at stamps[PV_TST_NET + 4 * workgroup ...]
 #define PV_TST_NET ((1u << 20) + (1u << 18))
 #define TST_WALL(P, k) if (threadIdx.x == 0) (P).stamps[PV_TST_NET + 4ull * blockIdx.x + (k)] = wall_clock64();
+// the start tick carries the workgroup's XCC id (HW_REG_XCC_ID, id 20, bits 3:0) in its top four bits
+#define TST_WALL_XCC(P) \
+    if (threadIdx.x == 0) (P).stamps[PV_TST_NET + 4ull * blockIdx.x] = (wall_clock64() & ~(0xfull << 60)) | (uint64_t)__builtin_amdgcn_s_getreg(20 | (3 << 11)) << 60;
 #else
+#define TST_WALL_XCC(P)
 #define TST_WALL(P, k)
 #endif
 __device__ __forceinline__ void net_ranges(PV_CREF(PvParams) P, bool contig, uint32_t &lb0, uint32_t &lb1, uint32_t &step)
@@ -2140,12 +2145,24 @@ __device__ __forceinline__ void net_ranges(PV_CREF(PvParams) P, bool contig, uin
     lb0 = blockIdx.x; lb1 = P.grid_main; step = gridDim.x;
     if (contig) { lb0 = min(blockIdx.x * P.cb_fan, P.grid_main); lb1 = min(lb0 + P.cb_fan, P.grid_main); step = 1; }
 }
-template <uint32_t NW, bool TC = false, bool FUSE = false>
-__device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
+// RING (pv_net_combine_ring, with FUSE): no IP log. A tile's IPv4 words and direction mask go to a
+// slot of the workgroup's ring in LDS, which the waves beside the Net phase insert from; the ring
+// has two sections, and one barrier a section (every PV_RING_K tiles of each wave: one turn of the
+// pipeline loop below) both publishes the section just filled and frees the other. Every wave runs
+// the range's section count of turns, a wave past its last tile filling its slots with zeros.
+struct FuseRing {
+    struct Sec {
+        uint32_t ip[PV_RING_SLOTS][PV_WT]; // a record's logged address: the IP log's word
+        uint64_t dm[PV_RING_SLOTS];        // a tile's direction mask: its ipdir word
+    } sec[2];
+};
+template <uint32_t NW, bool TC = false, bool FUSE = false, bool RING = false>
+__device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp, FuseRing *ring = nullptr)
 {
+    static_assert(!RING || (FUSE && TC && NW == PV_RING_WAVES), "the ring is the fused kernel's");
     PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
     __shared__ NetRegState S;
-    TST_WALL(P, 0)
+    TST_WALL_XCC(P)
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     for (uint32_t b = threadIdx.x; b < PV_HBINS; b += (FUSE ? 64u * NW : blockDim.x)) S.hist[b] = 0;
     if (threadIdx.x == 0) { S.nd = 0; S.nx = 0; S.ns = 0; }
@@ -2170,6 +2187,7 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
     NetCtr c;
     c.zero();
     bool any = false;
+    uint32_t secn = 0; // RING: sections filled so far (its low bit: the section being filled)
     // each workgroup walks the ranges of several grid workgroups (lb = blockIdx.x, + gridDim.x,
     // ...): the DNS pass, combine and merge keep the grid's partition, while the Net pass runs
     // one workgroup per CU (fewer, longer streams measured faster: tools/gpu_reg2.sh)
@@ -2185,7 +2203,9 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
     const uint64_t wend = min<uint64_t>(wbeg + P.wt_per_block, nwt);
     const uint32_t ntl = wend > wbeg + wave ? (uint32_t)((wend - wbeg - wave + NW - 1) / NW) : 0u;
     any |= ntl != 0;
-    auto tile_of = [&](uint32_t k) -> uint64_t { return wbeg + wave + (uint64_t)NW * min(k, ntl - 1); };
+    // RING: the turns of the pipeline loop, the same in every wave of the workgroup
+    const uint32_t nsk = RING ? pv_ring_sections(wend > wbeg ? (uint32_t)(wend - wbeg) : 0u) * PV_RING_K : 0u;
+    auto tile_of = [&](uint32_t k) -> uint64_t { return wbeg + wave + (uint64_t)NW * min(k, RING && !ntl ? 0u : ntl - 1); };
     auto off_of = [&](uint32_t k) -> uint32_t { return offs[min<uint64_t>(tile_of(k) * PV_WT + lane, last)]; };
     // one tile from its windows W (off: this lane's record start)
     // (a tile past the wave's last, live false, is a clamped copy: it parses nothing and its
@@ -2272,13 +2292,27 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
                 const bool v4 = ek && ((ek >> 32) & ~1ull) == (P.ip_base >> 32);
                 const uint64_t xm = __ballot(active && ek && !v4);
                 const uint64_t dbit = __ballot(v4 && ((ek >> 32) & 1));
-                if (TC) {
+                if constexpr (RING) {
+                    // (k < nsk: the loop's turns are whole sections)
+                    FuseRing::Sec &rs = ring->sec[secn & 1];
+                    const uint32_t q = pv_ring_slot(wave, k);
+                    rs.ip[q][lane] = active && v4 ? (uint32_t)ek : 0u;
+                    if (lane == 0) rs.dm[q] = dbit;
+                } else if (TC) {
                     // every lane (the log has 64 words of slack past the batch) and every lane
                     // the same direction word: two unconditional store instructions
+                    // (-DPV_FUSE_NOSTORE, a probe build: the fused kernel without them, to bound
+                    // what they cost. Its results are right only where an unfused batch has
+                    // logged the same records before: profiles/r11/fused_ring)
+#ifdef PV_FUSE_NOSTORE
+                    if constexpr (!FUSE)
+#endif
+                    {
                     PV_G uint32_t *const l32 = live ? P.iplog32 + i : reinterpret_cast<PV_G uint32_t *>(trash) + lane;
                     PV_G uint64_t *const ldw = live ? P.ipdir + t : trash + 32;
                     *l32 = active && v4 ? (uint32_t)ek : 0u;
                     *ldw = dbit;
+                    }
                 } else if (live) {
                     if (active) P.iplog32[i] = v4 ? (uint32_t)ek : 0u;
                     if (lane == 0) P.ipdir[t] = dbit;
@@ -2311,12 +2345,13 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
     // parse it should overlap into a loop exit's branch (the conditional form: 237 -> 229 us on C2,
     // profiles/r6). Loads retire in order, so each counted wait the compiler places for a tile's
     // windows leaves the younger loads and the previous tiles' stores in flight.
-    if (ntl) {
+    static_assert(PV_RING_K == 3, "a section is one turn of the pipeline loop");
+    if (RING ? nsk : ntl) {
         uint4 W0[5], W1[5], W2[5];
         uint32_t o0 = off_of(0), o1 = off_of(1), o2 = off_of(2);
         win_load(recs, o0, W0);
         win_load(recs, o1, W1);
-        for (uint32_t k = 0; k < ntl; k += 3) {
+        for (uint32_t k = 0; k < (RING ? nsk : ntl); k += 3) {
             const uint32_t oN = off_of(k + 3);
             win_load(recs, o2, W2);  // tile k + 2
             tile(k, o0, W0);
@@ -2329,13 +2364,18 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp)
             o1 = oN1;
             tile(k + 2, o2, W2);
             o2 = oN2;
+            if constexpr (RING) {
+                lds_barrier(); // the section's slots are written (lgkmcnt(0)): published
+                secn++;
+            }
         }
     }
     // this range's DNS list: its count, and the slot counter reset for the next range (LDS-only
     // barriers: the range's IP-log and DNS-list stores are other kernels' to read, and waiting
     // for them here would stall every wave on their completion; FUSE: the waves beside the Net
     // phase read the range's IP log after these barriers, so there the wait is taken)
-    if constexpr (FUSE) __builtin_amdgcn_s_waitcnt(PV_WAIT_VMCNT0);
+    // (RING: no log, nothing to wait for)
+    if constexpr (FUSE && !RING) __builtin_amdgcn_s_waitcnt(PV_WAIT_VMCNT0);
     lds_barrier();
     if (threadIdx.x == 0) {
         P.mq_cnt[lb] = 0;
@@ -3358,6 +3398,16 @@ __device__ __forceinline__ T ld_own(const PV_G T *p)
     if constexpr (FUSE) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else return *p;
 }
+// pv_net_combine_ring's ring (the fused kernel without it has none)
+template <bool RING>
+__device__ __forceinline__ FuseRing *fuse_ring()
+{
+    if constexpr (RING) {
+        __shared__ FuseRing r;
+        return &r;
+    } else
+        return nullptr;
+}
 // topn_combine's init by other threads than its own (tid of nt): the table, region counters and
 // table words cleared
 template <uint32_t CN, class St>
@@ -3409,7 +3459,12 @@ __device__ __forceinline__ void comb_crange_own(PV_CREF(PvParams) P, St &S, PV_G
 // starts on this CU as soon as its own ranges are logged. (The hand-over alone, with the whole
 // combine behind the last range, gained nothing: the slowest CU's Net phase is no shorter and its
 // whole combine still followed it. -DPV_FUSE_NO_EARLY builds that form; profiles/r10/fused_plain.)
-template <uint32_t CN, uint32_t NR, bool FUSE = false>
+// RING (pv_net_combine_ring): the host launches it only where every workgroup's group is compact
+// on the parameters alone (pv_host.cpp: `early` below, a single-range group allowed); the Net waves
+// log nothing and hand each tile's words over in LDS
+// (FuseRing), every range is inserted beside the Net phase, a section at a time, and nothing is
+// left to insert after the hand-over.
+template <uint32_t CN, uint32_t NR, bool FUSE = false, bool RING = false>
 __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams *__restrict__ Pp = nullptr)
 {
     using St = CombState<CN, NR>;
@@ -3430,10 +3485,46 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
         early = CAN && P.cb_compact && e1 > e0 + 1 && P.ip_compact && (P.net_groups & PV_NET_TOP_IPS_BIT) && blockDim.x == PV_CB_THREADS &&
                 ey - ea <= 65535;
 #endif
+        FuseRing *const ring = fuse_ring<RING>();
+        if constexpr (RING) {
+            static_assert(CAN && sizeof(St) + sizeof(NetRegState) + sizeof(FuseRing) <= 160 * 1024, "pv_net_combine_ring: the ring beside them");
+            static_assert(PV_CB_THREADS == 64 * (NETW + PV_RING_SLOTS), "an inserting thread a slot's lane");
+            early = true; // the host's word: checked there, for every workgroup
+        }
         if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < NETW) {
-            net_fast_reg<NETW, true, true>(Pp);
+            net_fast_reg<NETW, true, true, RING>(Pp, ring);
             // hand-over, this side: every store of the Net phase acknowledged by the L2
             __builtin_amdgcn_s_waitcnt(PV_WAIT_VMCNT0);
+        } else if constexpr (RING) {
+            // the Net phase's barriers, as below, and one a section in between: after it the
+            // section's twelve slots are complete and the other section is the Net waves' to fill,
+            // until this wave arrives at the next barrier. Thread tid takes lane tid % 64 of slot
+            // tid / 64. The section counts are the Net waves' own (net_fast_reg's nsk).
+            const uint32_t tid = threadIdx.x - 64u * NETW, nt = blockDim.x - 64u * NETW;
+            const uint32_t slot = tid >> 6, lane = tid & 63;
+            PV_G ulonglong2 *const sp = reinterpret_cast<PV_G ulonglong2 *>(P.tp_buf) + (uint64_t)e0 * P.mq_cap;
+            const uint64_t nwt = (P.n + PV_WT - 1) / PV_WT;
+            lds_barrier();
+            comb_init<CN>(S, 2u << P.reg_log2, tid, nt);
+            uint32_t secn = 0;
+            for (uint32_t gr = e0; gr < e1; gr++) {
+                const uint64_t wbeg = (uint64_t)gr * P.wt_per_block, wend = min<uint64_t>(wbeg + P.wt_per_block, nwt);
+                const uint32_t ns = pv_ring_sections(wend > wbeg ? (uint32_t)(wend - wbeg) : 0u);
+                const uint32_t ra = (uint32_t)(wbeg * PV_WT - ea); // (a range with a section has records: wbeg * 64 < n)
+                for (uint32_t s = 0; s < ns; s++, secn++) {
+                    lds_barrier();
+                    const FuseRing::Sec &rs = ring->sec[secn & 1];
+                    const uint32_t ip = rs.ip[slot][lane];
+                    if (ip) {
+                        const uint32_t dir = (uint32_t)(rs.dm[slot] >> lane) & 1u, pos = comb_cpos<2 * CN>(ip, dir);
+                        comb_cadd_pre<2 * CN>(P, S, sp, ip, dir, (uint32_t)ea, ra + (pv_ring_tile(s, slot) * PV_WT + lane), pos, S.ckey[pos],
+                                              (S.crep[pos >> 1] >> (16u * (pos & 1u))) & 0xffffu);
+                    }
+                }
+                lds_barrier();
+                lds_barrier();
+            }
+            lds_barrier();
         } else {
             // the Net phase's init barrier first (the Net waves start streaming at once), then
             // the clear, then its other barriers, two a range and the last: parked at s_barrier, no
@@ -3488,7 +3579,8 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
     uint32_t cbase = 0; // the group's first record
     uint32_t other = 1;
     if constexpr (CAN) {
-        if (P.cb_compact && g1 - g0 > 1 && P.ip_compact && (P.net_groups & PV_NET_TOP_IPS_BIT) && blockDim.x == PV_CB_THREADS) {
+        // (RING: a last group of one range is compact too, its words having come through the ring)
+        if (P.cb_compact && (RING || g1 - g0 > 1) && P.ip_compact && (P.net_groups & PV_NET_TOP_IPS_BIT) && blockDim.x == PV_CB_THREADS) {
             uint64_t a0, z0, a1, z1;
             wg_records(P, g0, a0, z0);
             wg_records(P, g1 - 1, a1, z1);
@@ -3505,7 +3597,8 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
     }
     if (threadIdx.x == 0) S.nsp = 0;
     }
-    const bool compact = CAN && __builtin_amdgcn_readfirstlane(other) == 0;
+    // (RING: compact on the host's word; the table is filled already)
+    const bool compact = RING || (CAN && __builtin_amdgcn_readfirstlane(other) == 0);
     if constexpr (!FUSE) __syncthreads();
     TST(0)
     if (compact) {
@@ -3513,7 +3606,7 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
             // the generic compact-log loop below with 4-B keys: PV_CB_U log words and direction
             // words in flight, then every first-probe key and index half, then the inserts
             const PV_G uint32_t *ip4 = P.iplog32;
-            for (uint32_t gr = FUSE && early ? g1 - 1 : g0; gr < g1; gr++) {
+            for (uint32_t gr = RING ? g1 : (FUSE && early ? g1 - 1 : g0); gr < g1; gr++) {
                 uint64_t a, z;
                 wg_records(P, gr, a, z);
                 const uint32_t nn = (uint32_t)(z - a), bd = blockDim.x, ra = (uint32_t)(a - cbase);
@@ -3704,6 +3797,46 @@ extern "C" __global__ void __launch_bounds__(PV_CB_THREADS) pv_net_combine_plain
 {
     PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
     topn_combine<PV_CB_CN, 2048, true>(P, Pp);
+}
+// The same without the IP log: the Net waves hand each tile's words to the inserting waves through
+// LDS (FuseRing), so the log's store, its read-back and the Net phase's waits for it are gone and
+// no range is left to insert on the slowest CU's tail (profiles/r11/fused_ring). Only where every
+// workgroup's group is compact on the host's parameters alone: the host's choice (pv_host.cpp).
+// A batch that turns out not to be plain has pv_net_iplog write the log the regular chain reads.
+extern "C" __global__ void __launch_bounds__(PV_CB_THREADS) pv_net_combine_ring(const PvParams *__restrict__ Pp)
+{
+    PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
+    topn_combine<PV_CB_CN, 2048, true, true>(P, Pp);
+}
+// The compact IP log of a batch pv_net_combine_ring ran on and the regular chain has to combine
+// after all: for every tile what pv_net_kernel_reg_tc stores (a word a lane, the 64 words of slack
+// past the batch included, and the tile's direction word), from the same loads and fast_fields;
+// no counter, histogram, list or status word. A wave a tile.
+extern "C" __global__ void __launch_bounds__(256) pv_net_iplog(const PvParams *__restrict__ Pp)
+{
+    PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const uint64_t n = P.n, nwt = (n + PV_WT - 1) / PV_WT;
+    HostNets h;
+    {
+        const uint32_t n4 = P.nets.n4;
+        h.a0 = P.nets.v4_addr[0]; h.m0 = P.nets.v4_mask[0]; h.e0 = n4 > 0 ? ~0u : 0u;
+        h.a1 = P.nets.v4_addr[1]; h.m1 = P.nets.v4_mask[1]; h.e1 = n4 > 1 ? ~0u : 0u;
+    }
+    for (uint64_t t = (uint64_t)blockIdx.x * 4 + wave; t < nwt; t += (uint64_t)gridDim.x * 4) {
+        const uint64_t i = t * PV_WT + lane;
+        const uint32_t off = P.offs[min<uint64_t>(i, n - 1)];
+        uint4 W[5];
+        win_load(P.recs, off, W);
+        RecW rw;
+        win_words(W, off & 3, rw);
+        const FastRec f = fast_fields(rw, h);
+        const uint32_t ip = f.dir == 0 ? rw.at(42) : rw.at(46);
+        const bool ipok = i < n && f.ok != 0 && f.dir != 2 && ip != 0;
+        const uint64_t dbit = __ballot(ipok && f.dir == 1);
+        P.iplog32[i] = ipok ? ip : 0u;
+        if (lane == 0) P.ipdir[t] = dbit;
+    }
 }
 extern "C" __global__ void __launch_bounds__(PV_CB_THREADS) pv_topn_combine_r12(const PvParams *__restrict__ Pp)
 {
