@@ -674,8 +674,8 @@ int pv_geodb_lookup(const pv_geodb *db, const uint8_t *addrs, size_t n, uint32_t
  * combine lists), summed by window merges, external buckets (by string) and the multi-GPU
  * reduce (pv_window_regions lists them). JSON, Prometheus and OpenTelemetry carry them
  * (geo_loc with lat / lon when both exist, asn). Not built, and refused with PV_EUNSUPPORTED
- * while a database is attached: Net v2, DNS v2, the DNS top_ecs group, the DNS geoloc_notfound /
- * asn_notfound filters and pv_process_dnstap. With top_ips disabled the passes still log the IP
+ * while a database is attached: Net v2, DNS v2, pv_process_dnstap, and, unless pv_set_dns_geo
+ * switched the DNS half on, the DNS top_ecs group and the DNS geoloc_notfound / asn_notfound filters. With top_ips disabled the passes still log the IP
  * entries the counts come from; the outputs then show no top_ipv4 / top_ipv6. The Net geo filters are not built either: they stay net_filter_all. */
 int pv_set_geodb(pv_ctx *ctx, const pv_geodb *city, const pv_geodb *asn);
 /* The Net v1 handler's geo filters, the typed form of the "geoloc_notfound", "asn_notfound",
@@ -701,6 +701,42 @@ typedef struct pv_net_filters {
     const char *const *asn_numbers;  /* digit strings */
 } pv_net_filters;
 int pv_set_net_filters(pv_ctx *ctx, const pv_net_filters *f);
+/* The DNS v1 handler's half of the attached databases, switched on explicitly (without this call
+ * pv_set_geodb keeps refusing a context with the DNS top_ecs group or a DNS geo filter, and every
+ * code path, launch and output is as before).
+ * Counts (DnsMetricsBucket::process_dns_layer, dns/v1/DnsStreamHandler.cpp:1026-1048): with
+ * top_ecs enabled, every deep, unfiltered query whose first additional record carries an EDNS
+ * Client Subnet (the condition of query_ecs and top_query_ecs) has the subnet looked up as a full
+ * address in each attached database: top_geoLoc_ecs / top_asn_ecs, exact counts per dictionary id
+ * and DNS bucket (pv_dns_ecs_geo: one lane per listed query). The address is what the reference
+ * keeps of the option (DnsAdditionalRecord.h:80-98): IPv4 the first four address bytes, IPv6 the
+ * first EIGHT only, missing bytes zero. A lookup that finds nothing counts as "Unknown". JSON
+ * carries both tops (lat / lon when both exist), Prometheus and OpenTelemetry dns_top_geoLoc_ecs
+ * (geo_loc, lat, lon) and dns_top_asn_ecs (asn); window merges, external buckets (by string) and
+ * the multi-GPU reduce (pv_window_regions) sum them.
+ * Filters (DnsStreamHandler::_filtering :619-642): geoloc_notfound passes a message only when the
+ * city database is attached and the message is a query with ARCOUNT > 0 whose first additional
+ * record is ECS with a non-empty subnet whose location equals "Unknown"; asn_notfound the same on
+ * the ASN database and string; with both set both must pass. Everything else is filtered (an
+ * event plus `filtered`), UDP and reassembled TCP alike. A family that is set while its database
+ * is not attached filters every DNS message (decided at the first batch). The verdict is computed
+ * ahead of the DNS pass (pv_dns_geo_verdict: one walk per message and family, one pass byte per
+ * dictionary id) and read by the pass's filter block.
+ * Call before the first batch, before or after pv_set_geodb / pv_set_dns_filters; NULL clears.
+ * Still refused with PV_EUNSUPPORTED: DNS v2, Net v2 and pv_process_dnstap with a database, and
+ * a DNS geo filter with deep_sample_rate below 100 (the deep-sampling prescan runs ahead of the
+ * work lists the verdict is computed over, so its filter restatement cannot read it). */
+typedef struct pv_dns_geo {
+    uint32_t enable;          /* nonzero: the DNS v1 handler reads the attached databases */
+    uint32_t geoloc_notfound; /* the typed "geoloc_notfound": true */
+    uint32_t asn_notfound;    /* the typed "asn_notfound": true */
+} pv_dns_geo;
+int pv_set_dns_geo(pv_ctx *ctx, const pv_dns_geo *cfg);
+/* While pv_set_kernel_timing is on, a context with the DNS geo switch brackets the DNS stage's
+ * kernels of every batch with HIP events: ms[0] pv_dns_geo_verdict, ms[1] the DNS pass, ms[2]
+ * pv_dns_ecs, ms[3] pv_dns_ecs_geo, summed in milliseconds over `launches` batches (a kernel that did
+ * not run adds the gap between its two markers). reset != 0 clears them. */
+int pv_dns_geo_timing(pv_ctx *ctx, double ms[4], uint64_t *launches, int reset);
 
 /* ---- The DHCP handler (DhcpStreamHandler, src/handlers/dhcp): the "dhcp" schema next to
  * "packets" and "dns". While it is attached every batch gets one more device pass

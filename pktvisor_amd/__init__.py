@@ -68,6 +68,10 @@ class pv_net_filters(ctypes.Structure):
                 ("n_asn_numbers", ctypes.c_uint32), ("asn_numbers", ctypes.POINTER(ctypes.c_char_p))]
 
 
+class pv_dns_geo(ctypes.Structure):
+    _fields_ = [("enable", ctypes.c_uint32), ("geoloc_notfound", ctypes.c_uint32), ("asn_notfound", ctypes.c_uint32)]
+
+
 class pv_dhcp_config(ctypes.Structure):
     _fields_ = [("xact_ttl_ms", ctypes.c_uint32), ("recorded_stream", ctypes.c_uint32), ("max_events", ctypes.c_uint32)]
 
@@ -90,12 +94,23 @@ def _dns_code(kind: int, name: str):
     return int(v.value) if load_library().pv_dns_code(kind, str(name).encode(), ctypes.byref(v)) == 0 else None
 
 
-def dns_filter_config(cfg: dict, v2: bool = False) -> dict:
+def dns_filter_config(cfg: dict, v2: bool = False, dns_geo: bool = False) -> dict:
     """DnsStreamHandler::start's filter setup (src/handlers/dns/v1/DnsStreamHandler.cpp:60-150):
-    typed values in, the pv_dns_filters fields out; ConfigError with the reference's text."""
+    typed values in, the pv_dns_filters fields out; ConfigError with the reference's text.
+    dns_geo (v1, pv_set_dns_geo): geoloc_notfound / asn_notfound are accepted and come back typed
+    under "dns_geo" (the pv_dns_geo fields)."""
     out = dict(exclude_noerror=0, only_rcode_mask=0, answer_count=-1, only_queries=0, only_responses=0, only_qtype=[],
                only_qname=[], only_qname_suffix=[], only_dnssec_response=0, filter_all=0,
                public_suffix_list=0)
+    if dns_geo and not v2:
+        cfg = dict(cfg)
+        geo = {"enable": 1}
+        for k in ("geoloc_notfound", "asn_notfound"):
+            v = cfg.pop(k, False)
+            if not isinstance(v, bool):
+                raise ConfigError(f"wrong type for key: {k}")
+            geo[k] = 1 if v else 0
+        out["dns_geo"] = geo
     for k in cfg:
         if k in DNS_FILTER_NOT_BUILT:
             raise ConfigError(f"DnsStreamHandler: filter {k} is not supported by the GPU handler")
@@ -192,7 +207,7 @@ EXPORTS = ["pv_version", "pv_device_count", "pv_create", "pv_destroy", "pv_last_
            "pv_topn_x_candidates", "pv_topn_x_names", "pv_topn_x_view", "pv_values_x_select", "pv_comm_values_select",
            "pv_slow_x_finish", "pv_comm_slow_finish", "pv_geodb_open", "pv_geodb_open_file", "pv_geodb_close",
            "pv_geodb_last_error", "pv_geodb_entries", "pv_geodb_hash", "pv_geodb_hashes", "pv_set_net_filters", "pv_geodb_entry", "pv_geodb_lookup", "pv_set_geodb",
-           "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing", "pv_set_bgp", "pv_bgp_timing", "pv_chain_stats", "pv_fuse_stats",
+           "pv_set_dns_geo", "pv_dns_geo_timing", "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing", "pv_set_bgp", "pv_bgp_timing", "pv_chain_stats", "pv_fuse_stats",
            "pv_ring_stats"]
 PV_GEODB_CITY, PV_GEODB_ASN = 0, 1
 # pv_allreduce_fn: (uint64_t *buf, size_t n, int op, void *user) -> int
@@ -381,6 +396,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                    ctypes.POINTER(ctypes.c_char_p)]
     lib.pv_geodb_lookup.argtypes = [P, P, ctypes.c_size_t, U32, P]
     lib.pv_set_geodb.argtypes = [P, P, P]
+    lib.pv_set_dns_geo.argtypes = [P, ctypes.POINTER(pv_dns_geo)]
+    lib.pv_dns_geo_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     lib.pv_geodb_lookup_device.argtypes = [P, U32, P, ctypes.c_size_t, U32, P]
     lib.pv_set_dhcp.argtypes = [P, ctypes.POINTER(pv_dhcp_config)]
     lib.pv_dhcp_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.c_int]
@@ -713,14 +730,21 @@ class PvHandlers:
                  net2_config: Optional[dict] = None, dns2_config: Optional[dict] = None,
                  deep_sample_rate: int = 100, tcp_packet_reassembly_cache_limit: int = 0, bpf=None,
                  tcp_exact_lru: bool = False, geo_city_db=None, geo_asn_db=None, dhcp_config: Optional[dict] = None,
-                 dhcp_max_events: int = 0, bgp_config: Optional[dict] = None, bgp_max_events: int = 0):
-        """dhcp_config: attaches the DHCP handler ("dhcp" schema, DhcpStreamHandler) with its config
+                 dhcp_max_events: int = 0, bgp_config: Optional[dict] = None, bgp_max_events: int = 0,
+                 dns_geo: bool = False):
+        """dns_geo: the DNS v1 handler reads the attached databases too (pv_set_dns_geo): with top_ecs
+        enabled, top_geoLoc_ecs / top_asn_ecs of the queries' ECS subnets, and the geoloc_notfound /
+        asn_notfound keys of dns_config / dns_filters as filters matched on the device.
+        dhcp_config: attaches the DHCP handler ("dhcp" schema, DhcpStreamHandler) with its config
         map (recorded_stream, xact_ttl_secs, xact_ttl_ms, the window keys); dhcp_max_events: the DHCP
         events one decode round stores (0: the default). bgp_config / bgp_max_events: the same for
         the BGP handler ("bgp" schema, BgpStreamHandler; recorded_stream and the window keys)."""
         from pktvisor_amd import config as pvcfg
         self.lib = load_library()
-        filt = dns_filter_config(dns_filters) if dns_filters else None
+        filt = dns_filter_config(dns_filters, dns_geo=dns_geo) if dns_filters else None
+        dgeo = {"enable": 1, "geoloc_notfound": 0, "asn_notfound": 0} if dns_geo else None
+        if filt and "dns_geo" in filt:
+            dgeo = filt.pop("dns_geo")
         net_filter_all = 0
         net_filters = None
         self.dnstap_mask = 0
@@ -751,13 +775,15 @@ class PvHandlers:
             topn_percentile_threshold = win.get("topn_percentile_threshold", topn_percentile_threshold)
             # (with a database attached the geo filters are typed and matched on the device)
             geo_on = (geo_city_db is not None, geo_asn_db is not None)
-            n, d = pvcfg.net_start(ncfg, geo_enabled=geo_on if any(geo_on) else None), pvcfg.dns_start(dcfg)
+            n = pvcfg.net_start(ncfg, geo_enabled=geo_on if any(geo_on) else None)
+            d = pvcfg.dns_start(dcfg, dns_geo=True) if dns_geo and dns2_config is None else pvcfg.dns_start(dcfg)
             net_filters = n.get("filters")
             if net_filters:
                 n["filter_all"] = False  # pv_set_net_filters decides, family by family
             net_groups, dns_groups, net_filter_all = n["groups"], d["groups"], int(n["filter_all"])
             if dns2_config is None:
                 filt = d["filters"]
+                dgeo = d.get("dns_geo", dgeo)
             if dns2_config is None:
                 self.dnstap_mask = d["dnstap_mask"]
             if d["xact_ttl_ms"] is not None and dns2_config is None:
@@ -808,6 +834,10 @@ class PvHandlers:
             # the pcap input's config (PcapInputStream.cpp:97-99)
             self._check(self.lib.pv_set_tcp_reassembly_limit(self.ctx, int(tcp_packet_reassembly_cache_limit)),
                         "pv_set_tcp_reassembly_limit")
+        if dgeo is not None:
+            # before the databases: pv_set_geodb's DNS refusals do not fire while it is on
+            g = pv_dns_geo(int(dgeo["enable"]), int(dgeo["geoloc_notfound"]), int(dgeo["asn_notfound"]))
+            self._check(self.lib.pv_set_dns_geo(self.ctx, ctypes.byref(g)), "pv_set_dns_geo")
         if tcp_exact_lru:
             # PcapInputStream's LRU of TCP connections replayed exactly (pv_set_tcp_exact_lru)
             self._check(self.lib.pv_set_tcp_exact_lru(self.ctx, 1), "pv_set_tcp_exact_lru")
@@ -848,6 +878,14 @@ class PvHandlers:
         ms, n = ctypes.c_double(), ctypes.c_uint64()
         self._check(self.lib.pv_dhcp_timing(self.ctx, ctypes.byref(ms), ctypes.byref(n), int(reset)), "pv_dhcp_timing")
         return ms.value, n.value
+
+    def dns_geo_timing(self, reset: bool = False):
+        """({kernel: ms summed}, batches) of the DNS stage's kernels over the batches processed while
+        set_kernel_timing is on, on a dns_geo context (pv_dns_geo_timing)"""
+        ms, n = (ctypes.c_double * 4)(), ctypes.c_uint64()
+        self._check(self.lib.pv_dns_geo_timing(self.ctx, ms, ctypes.byref(n), int(reset)), "pv_dns_geo_timing")
+        names = ("pv_dns_geo_verdict", "pv_dns_kernel", "pv_dns_ecs", "pv_dns_ecs_geo")
+        return {k: float(v) for k, v in zip(names, ms)}, int(n.value)
 
     def chain_stats(self, reset: bool = False):
         """(short-chain batches, of those fallen back, late names launches, regular-chain batches) since the
@@ -1334,7 +1372,8 @@ def last_record_ts(recs: bytes, index: RecordIndex, ts_nano: int = 0):
 
 
 def pktvisor_reader(path: str, host_spec: Optional[str] = None, periods: int = 5, **kw) -> dict:
-    """GPU equivalent of `pktvisor-reader [-H host_spec] --periods N FILE` for net + dns."""
+    """GPU equivalent of `pktvisor-reader [-H host_spec] --periods N FILE` for net + dns.
+    dns_geo=True (with geo_city_db / geo_asn_db): the DNS handler's half of the databases, as PvHandlers takes it."""
     linktype, ts_nano, recs = read_pcap(path)
     bpf = kw.pop("bpf", None)
     if bpf:

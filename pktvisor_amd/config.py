@@ -266,9 +266,11 @@ def dns2_start(cfg: dict) -> dict:
     return {"groups": groups | GROUPS_SET, "filters": filters, "xact_ttl_ms": ttl, "dnstap_mask": mask}
 
 
-def dns_start(cfg: dict) -> dict:
+def dns_start(cfg: dict, dns_geo: bool = False) -> dict:
     """DnsStreamHandler::start (src/handlers/dns/v1/DnsStreamHandler.cpp:43-201) up to the signal
-    wiring: {"groups": bits | GROUPS_SET, "filters": pv_dns_filters fields, "xact_ttl_ms": int|None}"""
+    wiring: {"groups": bits | GROUPS_SET, "filters": pv_dns_filters fields, "xact_ttl_ms": int|None}.
+    dns_geo: the handler reads the attached GeoIP databases (pv_set_dns_geo); geoloc_notfound /
+    asn_notfound are then typed, under "dns_geo" (the pv_dns_geo fields), instead of filter_all."""
     from pktvisor_amd import dns_filter_config
     validate_configs(cfg, DNS_CONFIG_DEFS)
     groups = process_groups(cfg, DNS_GROUP_DEFS, DNS_DEFAULT_GROUPS)
@@ -277,6 +279,13 @@ def dns_start(cfg: dict) -> dict:
     filters = dns_filter_config({k: cfg[k] for k in fkeys if k in cfg})
     # with no geo database enabled, geoloc_notfound / asn_notfound filter every packet (:619-642)
     filters["filter_all"] = 1 if (_bool(cfg, "geoloc_notfound") or _bool(cfg, "asn_notfound")) else 0
+    geo = None
+    if dns_geo:
+        # matched on the device against the attached databases; a family whose database is not
+        # attached filters every message there (the reference's !enabled() branch)
+        geo = {"enable": 1, "geoloc_notfound": 1 if _bool(cfg, "geoloc_notfound") else 0,
+               "asn_notfound": 1 if _bool(cfg, "asn_notfound") else 0}
+        filters["filter_all"] = 0
     if "dnstap_msg_type" in cfg and cfg["dnstap_msg_type"] not in DNSTAP_MSG_TYPES:
         raise ConfigException("DnsStreamHandler: dnstap_msg_type contained an invalid/unsupported type. Valid types: "
                               + ", ".join(DNSTAP_MSG_TYPES))
@@ -292,4 +301,7 @@ def dns_start(cfg: dict) -> dict:
     if "dnstap_msg_type" in cfg:
         q, r = DNSTAP_TYPE_PAIRS[cfg["dnstap_msg_type"]]
         mask = (1 << q) | (1 << r)
-    return {"groups": groups | GROUPS_SET, "filters": filters, "xact_ttl_ms": ttl, "dnstap_mask": mask}
+    out = {"groups": groups | GROUPS_SET, "filters": filters, "xact_ttl_ms": ttl, "dnstap_mask": mask}
+    if geo is not None:
+        out["dns_geo"] = geo
+    return out

@@ -126,6 +126,8 @@ void clear_part(pv_ctx *c, int part, uint32_t s)
     } else {
         launch_fill64(c, sum + PV_OFF_DNS, PV_SUM_WORDS - PV_OFF_DNS, 0);
         launch_fill64(c, cpc + PV_MIN_NET_WORDS, PV_MIN_WORDS - PV_MIN_NET_WORDS, (uint64_t)PV_CPC_EMPTY);
+        for (auto &g : c->geo)
+            if (g.d_dcnt) launch_fill64(c, (uint64_t *)g.d_dcnt + (uint64_t)s * g.dict.size(), g.dict.size(), 0);
     }
     // keys only: a count or name word is read only behind a non-zero key, and whoever
     // claims an entry overwrites its name word and adds net of the stale count (global_add,
@@ -328,8 +330,11 @@ int pv_set_geodb(pv_ctx *c, const pv_geodb *city, const pv_geodb *asn)
         // what a database would have to feed and does not yet: refused, not approximated
         if (c->net2_groups) return c->fail(PV_EUNSUPPORTED, "geo databases: the Net v2 handler's top_geo is not built");
         if (c->dns2_groups) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS v2 handler's geo metrics are not built");
-        if (c->dns_groups & PV_DNS_TOP_ECS) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS top_ecs group's geo metrics are not built");
-        if (c->f_flags & PVDF_FILTER_ALL) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS geoloc_notfound / asn_notfound filters are not built");
+        // (the DNS v1 half is opt-in, pv_set_dns_geo: without it both stay refused)
+        if (!c->dg_on && (c->dns_groups & PV_DNS_TOP_ECS))
+            return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS top_ecs group's geo metrics are not built");
+        if (!c->dg_on && (c->f_flags & PVDF_FILTER_ALL))
+            return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS geoloc_notfound / asn_notfound filters are not built");
     }
     hipError_t e = hipSetDevice(c->device);
     if (!hip_ok(e)) return c->hipfail(e, "geo database");
@@ -338,6 +343,7 @@ int pv_set_geodb(pv_ctx *c, const pv_geodb *city, const pv_geodb *asn)
     auto drop = [](pv_ctx::GeoAttach &g) {
         if (g.d_tree) hipFree(g.d_tree);
         if (g.d_cnt) hipFree(g.d_cnt);
+        if (g.d_dcnt) hipFree(g.d_dcnt);
         g = pv_ctx::GeoAttach();
     };
     for (uint32_t k = 0; k < 2; k++) {
@@ -363,7 +369,11 @@ int pv_set_geodb(pv_ctx *c, const pv_geodb *city, const pv_geodb *asn)
     for (uint32_t k = 0; k < 2; k++) {
         drop(c->geo[k]);
         c->geo[k] = std::move(next[k]);
+        // (DNS geo: the pass tables follow the dictionaries; dg_setup builds them and the counts again)
+        if (c->d_dg_pass[k]) hipFree(c->d_dg_pass[k]);
+        c->d_dg_pass[k] = nullptr;
     }
+    c->dg_ready = false;
     return nf_build(c); // (filters set earlier match the new dictionaries)
 }
 
@@ -427,6 +437,83 @@ int pv_set_net_filters(pv_ctx *c, const pv_net_filters *f)
         return c->fail(PV_EUNSUPPORTED, "deep_sample_rate below 100 with geo filters is not built");
     for (int k = 0; k < 2; k++) { c->nf_on[k] = on[k]; c->nf_prefix[k] = pre[k]; }
     return nf_build(c);
+}
+
+int pv_set_dns_geo(pv_ctx *c, const pv_dns_geo *cfg)
+{
+    if (!c) return PV_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->records_seen) return c->fail(PV_EINVAL, "the DNS geo switch must be set before the first batch");
+    const bool on = cfg && cfg->enable;
+    const bool nf[2] = {on && cfg->geoloc_notfound, on && cfg->asn_notfound};
+    if (on && (c->geo[0].on || c->geo[1].on)) {
+        if (c->net2_groups) return c->fail(PV_EUNSUPPORTED, "geo databases: the Net v2 handler's top_geo is not built");
+        if (c->dns2_groups) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS v2 handler's geo metrics are not built");
+    }
+    if (on && c->dns2_groups && (nf[0] || nf[1]))
+        return c->fail(PV_EUNSUPPORTED, "geoloc_notfound / asn_notfound are not DNS v2 filters here");
+    // (the deep-sampling prescans restate the filter chain ahead of the DNS work lists the verdict is
+    // computed over: they cannot read it)
+    if ((nf[0] || nf[1]) && c->sample_rate < 100)
+        return c->fail(PV_EUNSUPPORTED, "deep_sample_rate below 100 with DNS geo filters is not built");
+    if (!on && (c->geo[0].on || c->geo[1].on) && ((c->dns_groups & PV_DNS_TOP_ECS) || (c->f_flags & PVDF_FILTER_ALL)))
+        return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS top_ecs group and geo filters need the DNS geo switch");
+    c->dg_on = on;
+    c->dg_nf[0] = nf[0];
+    c->dg_nf[1] = nf[1];
+    c->dg_ready = false; // (dg_setup builds what the new setting needs)
+    return 0;
+}
+
+// DNS v1 geo at the first batch (the databases, the filters and the switch are all set by then):
+// the DNS slots' dense counts, the address lists next to the top_ecs list, the pass tables (1
+// where the dictionary entry's string is exactly "Unknown") and the verdict bytes. A steady-state
+// batch allocates nothing here (the TCP buffers hold the message list's fixed capacity).
+extern "C++" int pvh::dg_setup(pv_ctx *c)
+{
+    if (c->dg_ready || !c->dg_on) return 0;
+    hipError_t e = hipSetDevice(c->device);
+    if (!hip_ok(e)) return c->hipfail(e, "DNS geo");
+    if (c->dg_counting()) {
+        for (auto &g : c->geo) {
+            if (!g.on || g.d_dcnt) continue;
+            const size_t cbytes = (size_t)PV_SLOTS * g.dict.size() * 8;
+            if (!hip_ok(e = hipMalloc(&g.d_dcnt, cbytes)) || !hip_ok(e = hipMemset(g.d_dcnt, 0, cbytes)))
+                return c->hipfail(e, "DNS geo counts");
+        }
+        if (!c->d_ecsg_tcp && !hip_ok(e = hipMalloc(&c->d_ecsg_tcp, (size_t)c->tmsg_cap * sizeof(uint4))))
+            return c->hipfail(e, "DNS geo TCP list");
+    }
+    if (c->dg_verdicts()) {
+        for (int k = 0; k < 2; k++) {
+            if (!c->dg_nf[k] || c->d_dg_pass[k]) continue;
+            const auto &dict = c->geo[k].dict;
+            std::vector<uint8_t> pass(dict.size(), 0);
+            for (size_t i = 0; i < dict.size(); i++) pass[i] = dict[i].name == "Unknown" ? 1 : 0;
+            if (!hip_ok(e = hipMalloc(&c->d_dg_pass[k], std::max<size_t>(pass.size(), 1))) ||
+                !hip_ok(e = hipMemcpy(c->d_dg_pass[k], pass.data(), pass.size(), hipMemcpyHostToDevice)))
+                return c->hipfail(e, "DNS geo pass table");
+        }
+        const size_t nv = (size_t)c->max_records + 64, nt = (size_t)c->tmsg_cap + 64;
+        if (!c->d_dgv && (!hip_ok(e = hipMalloc(&c->d_dgv, nv)) || !hip_ok(e = hipMemset(c->d_dgv, 1, nv))))
+            return c->hipfail(e, "DNS geo verdicts");
+        if (!c->d_dgv_tcp && (!hip_ok(e = hipMalloc(&c->d_dgv_tcp, nt)) || !hip_ok(e = hipMemset(c->d_dgv_tcp, 1, nt))))
+            return c->hipfail(e, "DNS geo verdicts");
+    }
+    for (auto &ev : c->dg_ev)
+        if (!ev && !hip_ok(e = hipEventCreate(&ev))) return c->hipfail(e, "DNS geo timing events");
+    c->dg_ready = true;
+    return 0;
+}
+
+int pv_dns_geo_timing(pv_ctx *c, double ms[4], uint64_t *launches, int reset)
+{
+    if (!c) return PV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int k = 0; k < 4 && ms; k++) ms[k] = c->dg_ms[k];
+    if (launches) *launches = c->dg_launches;
+    if (reset) { c->dg_ms[0] = c->dg_ms[1] = c->dg_ms[2] = c->dg_ms[3] = 0; c->dg_launches = 0; }
+    return 0;
 }
 
 int pv_geodb_hashes(pv_ctx *c, uint64_t hashes[2])
@@ -566,7 +653,7 @@ int pv_set_dns_filters(pv_ctx *c, const pv_dns_filters *f)
     if (f->only_queries) fl |= PVDF_ONLY_QUERIES;
     if (f->only_responses) fl |= PVDF_ONLY_RESPONSES;
     if (f->only_dnssec_response) fl |= PVDF_ONLY_DNSSEC;
-    if (f->filter_all && (c->geo[0].on || c->geo[1].on))
+    if (f->filter_all && !c->dg_on && (c->geo[0].on || c->geo[1].on))
         return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS geoloc_notfound / asn_notfound filters are not built");
     if (f->filter_all) fl |= PVDF_FILTER_ALL;
     if (f->n_qtypes > PV_MAX_QTYPES) return c->fail(PV_EINVAL, "only_qtype: at most %d qtypes", PV_MAX_QTYPES);
@@ -807,7 +894,13 @@ void pv_destroy(pv_ctx *c)
     for (auto &g : c->geo) {
         if (g.d_tree) hipFree(g.d_tree);
         if (g.d_cnt) hipFree(g.d_cnt);
+        if (g.d_dcnt) hipFree(g.d_dcnt);
     }
+    for (void *p : {(void *)c->d_dg_pass[0], (void *)c->d_dg_pass[1], (void *)c->d_dgv, (void *)c->d_dgv_tcp, (void *)c->d_ecsg,
+                    (void *)c->d_ecsg_tcp})
+        if (p) hipFree(p);
+    for (hipEvent_t ev : c->dg_ev)
+        if (ev) hipEventDestroy(ev);
     if (c->d_dbits) hipFree(c->d_dbits);
     for (void *hp : {(void *)c->h_params, (void *)c->h_xparams, (void *)c->h_status, (void *)c->h_dbits, (void *)c->h_tcpcnt,
                      (void *)c->h_tparams})
@@ -1081,7 +1174,10 @@ void params_common(pv_ctx *c, PvParams &P, const uint8_t *d_recs, const uint32_t
     P.net_filter_all = (c->cfg.net_filter_all || c->nf_all()) ? 1u : 0u;
     P.gfilt = c->nf_verdicts() ? (const uint64_t *)c->d_gfilt : nullptr;
     P.nets = c->nets;
-    P.f_flags = c->f_flags;
+    // (DNS geo filters, pv_set_dns_geo: a family without its database filters every message; else
+    // the verdict bytes pv_dns_geo_verdict writes ahead of the DNS pass)
+    P.f_flags = c->f_flags | (c->dg_all() ? (uint32_t)PVDF_FILTER_ALL : 0u) | (c->dg_verdicts() ? (uint32_t)PVDF_GEO_VERDICT : 0u);
+    P.dgv = c->dg_verdicts() ? c->d_dgv : nullptr;
     P.f_rcode_mask = c->f_rcode_mask;
     P.f_ancount = c->f_ancount;
     P.f_nq = c->f_nq;
@@ -1571,12 +1667,30 @@ int tcp_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, uint64_t
     return 0;
 }
 
+// the attached databases as the geo kernels take them; dns: counting into the DNS slots' arrays
+static PvGeoArgs geo_args(const pv_ctx *c, bool dns)
+{
+    PvGeoArgs G{};
+    for (int k = 0; k < 2; k++) {
+        const pv_ctx::GeoAttach &g = c->geo[k];
+        if (!g.on) continue;
+        G.tree[k] = g.d_tree;
+        G.cnt[k] = dns ? g.d_dcnt : g.d_cnt;
+        G.node_count[k] = g.node_count;
+        G.start4[k] = g.start4;
+        G.ip_version[k] = g.ip_version;
+        G.entries[k] = (uint32_t)g.dict.size();
+    }
+    return G;
+}
+
 // The TCP DNS pass of a span: the batch's messages with ord in [4 * a, 4 * b), events in
 // the workgroup regions behind the span's grid; returns the workgroups it used
 uint32_t tcp_pass(pv_ctx *c, const PvParams &P, uint64_t a, uint64_t b, hipStream_t st, PvParams *d_slot)
 {
     if (!c->tcp_nmsg) return 0;
     PvParams Q = P;
+    Q.dgv = c->dg_verdicts() ? c->d_dgv_tcp : nullptr; // per message (pv_dns_geo_verdict, tcp)
     Q.recs = c->d_marena;
     Q.offs = c->d_moffs;
     Q.linktype = 101;
@@ -1593,7 +1707,15 @@ uint32_t tcp_pass(pv_ctx *c, const PvParams &P, uint64_t a, uint64_t b, hipStrea
     const uint32_t gt = (uint32_t)((c->tcp_nmsg + region - 1) / region);
     *d_slot = Q; // pinned host staging of the second parameter block
     hipMemcpyAsync(c->d_params + 1, d_slot, sizeof Q, hipMemcpyHostToDevice, st);
+    if (c->dg_verdicts())
+        hipLaunchKernelGGL(pv_dns_geo_verdict, dim3(std::min<uint32_t>((c->tcp_nmsg + 255) / 256, (uint32_t)c->cus * 8)), dim3(256), 0, st,
+                           (const PvParams *)(c->d_params + 1), geo_args(c, true), (const uint8_t *)(c->dg_nf[0] ? c->d_dg_pass[0] : nullptr),
+                           (const uint8_t *)(c->dg_nf[1] ? c->d_dg_pass[1] : nullptr), c->d_dgv_tcp, c->tmsg_cap, 1u);
     hipLaunchKernelGGL(pv_dns_tcp, dim3(gt), dim3(256), 0, st, (const PvParams *)(c->d_params + 1));
+    // DNS geo: the subnets of the ECS queries the pass listed (at most one per message)
+    if (Q.ecs_geo_tcp)
+        hipLaunchKernelGGL(pv_dns_ecs_geo, dim3(std::min<uint32_t>((c->tcp_nmsg + 255) / 256, (uint32_t)c->cus * 2)), dim3(256), 0, st,
+                           (const uint4 *)c->d_ecsg_tcp, (const uint32_t *)(c->d_status + ST_NECS_TCP), c->tmsg_cap, geo_args(c, true));
     return gt;
 }
 
@@ -2099,6 +2221,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     // record kernel runs; the flush's messages, ranked at a record 0, go through the TCP DNS pass
     // and the transaction stage as any span's do.
     const uint64_t nord = n ? n : 1;
+    if (int rc = dg_setup(c)) return rc;
     PvParams P;
     params_common(c, P, d_recs, d_offs, n);
     // a batch with no TCP stage ahead of it is one span: its Net pass emits the TCP segments
@@ -2392,6 +2515,20 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         }
         P.ecs_list = reinterpret_cast<uint32_t *>(c->d_ecs);
         P.ecs_cap = (uint32_t)c->ecs_cap;
+        if (c->dg_counting()) {
+            // DNS geo: the queries' addresses at the same ranks, and the TCP pass's own list
+            if (c->ecsg_cap < c->ecs_cap) {
+                if (c->d_ecsg) hipFree(c->d_ecsg);
+                c->d_ecsg = nullptr;
+                c->ecsg_cap = 0;
+                if (!hip_ok(e = hipMalloc(&c->d_ecsg, (size_t)c->ecs_cap * sizeof(uint4)))) return c->hipfail(e, "top_ecs address list");
+                c->ecsg_cap = c->ecs_cap;
+            }
+            P.ecs_geo = reinterpret_cast<uint32_t *>(c->d_ecsg);
+            P.ecs_geo_tcp = reinterpret_cast<uint32_t *>(c->d_ecsg_tcp);
+            P.n_ecs_tcp = c->d_status + ST_NECS_TCP;
+            P.ecs_tcp_cap = c->tmsg_cap;
+        }
     }
     *c->h_params = P;
     if (!hip_ok(e = fill_and_upload(c, c->d_params, c->h_params, sizeof P, st)))
@@ -2462,8 +2599,20 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     }
     const bool sfx = (P.f_flags & (PVDF_ONLY_QSUFFIX | PVDF_PSL)) != 0;
     // the DNS stage: the suffix sizes, the DNS pass, its top_ecs updates, Net v2
+    // (pv_set_kernel_timing on a DNS geo context: events around the stage's kernels, read after the chain)
+    const bool dg_timed = c->timing_every && c->dg_on && c->dg_ev[4];
+    bool dg_stamped = false;
+    auto dg_mark = [&](int k) { if (dg_timed) hipEventRecord(c->dg_ev[k], st); };
     auto dns_stage = [&]() {
         if (sfx) hipLaunchKernelGGL(pv_dns_suffix, dim3(grid), dim3(256), 0, st, (const PvParams *)c->d_params);
+        dg_mark(0);
+        dg_stamped = dg_timed;
+        // DNS geo filters: the verdict of every message on the work lists, for the pass's filter block
+        if (P.dgv)
+            hipLaunchKernelGGL(pv_dns_geo_verdict, dim3(grid), dim3(256), 0, st, (const PvParams *)c->d_params, geo_args(c, true),
+                               (const uint8_t *)(c->dg_nf[0] ? c->d_dg_pass[0] : nullptr),
+                               (const uint8_t *)(c->dg_nf[1] ? c->d_dg_pass[1] : nullptr), c->d_dgv, (uint32_t)(c->max_records + 64), 0u);
+        dg_mark(1);
         // the DNS pass walks the logical grid's ranges with its resident grid
         const uint32_t dns_grid = std::min<uint32_t>(grid, (uint32_t)(c->cus * c->dns_wg_per_cu));
         if (sfx)
@@ -2472,8 +2621,15 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
             hipLaunchKernelGGL(pv_dns_kernel_f, dim3(dns_grid), dim3(64 * PV_DNS_WAVES), 0, st, (const PvParams *)c->d_params);
         else
             hipLaunchKernelGGL(pv_dns_kernel, dim3(dns_grid), dim3(64 * PV_DNS_WAVES), 0, st, (const PvParams *)c->d_params);
+        dg_mark(2);
         if (c->dns_groups & PV_DNS_TOP_ECS)
             hipLaunchKernelGGL(pv_dns_ecs, dim3((uint32_t)c->cus * 2), dim3(256), 0, st, (const PvParams *)c->d_params);
+        dg_mark(3);
+        // DNS geo: top_geoLoc_ecs / top_asn_ecs of the same list's queries
+        if (P.ecs_geo)
+            hipLaunchKernelGGL(pv_dns_ecs_geo, dim3((uint32_t)c->cus * 2), dim3(256), 0, st, (const uint4 *)c->d_ecsg,
+                               (const uint32_t *)(c->d_status + ST_NECS), P.ecs_cap, geo_args(c, true));
+        dg_mark(4);
         if (c->net2_groups) hipLaunchKernelGGL(pv_net2_kernel, dim3(grid), dim3(256), 0, st, (const PvParams *)c->d_params);
     };
     // top-N: combine each workgroup's updates into a list sorted by table region, merge
@@ -2561,6 +2717,16 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         c->chain_n[2]++;
         names_stage();
         if (!hip_ok(e = read_status())) return c->hipfail(e, "kernel execution");
+    }
+    if (dg_stamped) {
+        // (read_status synchronised the stream behind the stage)
+        bool ok = true;
+        float part[4];
+        for (int k = 0; k < 4 && ok; k++) ok = hipEventElapsedTime(&part[k], c->dg_ev[k], c->dg_ev[k + 1]) == hipSuccess;
+        if (ok) {
+            for (int k = 0; k < 4; k++) c->dg_ms[k] += part[k];
+            c->dg_launches++;
+        }
     }
     if (n) {
         c->dns_heavy = (uint64_t)status[ST_NDNS] * 2 > n;

@@ -165,6 +165,9 @@ extern "C" uint32_t pv_topn_merge_threads();
 extern "C" __global__ void pv_geo_walk(const uint32_t *tree, uint32_t node_count, uint32_t start, const uint32_t *addrs, uint64_t n,
                                        uint32_t addr_words, uint32_t *ids);
 extern "C" __global__ void pv_geo_count(const PvParams *P, PvGeoArgs G);
+extern "C" __global__ void pv_dns_ecs_geo(const uint4 *list, const uint32_t *n_list, uint32_t cap, PvGeoArgs G);
+extern "C" __global__ void pv_dns_geo_verdict(const PvParams *P, PvGeoArgs G, const uint8_t *pass_city, const uint8_t *pass_asn,
+                                              uint8_t *out, uint32_t out_cap, uint32_t tcp);
 extern "C" __global__ void pv_geo_verdict(const PvParams *P, PvGeoArgs G, const uint8_t *pass_city, const uint8_t *pass_asn,
                                           unsigned long long *out);
 struct PvBpfIns;
@@ -247,7 +250,8 @@ namespace pvh {
 enum { ST_FLAGS = 0, ST_NEV = 1, ST_NRESP = 2, ST_NVALS = 3, ST_NDNS = 4, ST_NNEW = 5, ST_TSEG = 6, ST_TSEG_BYTES = 7,
        ST_HANDS = 8 /* top-N handlers with entries (device only) */, ST_NKEYS = 9 /* key-list length */,
        ST_NSLOW = 10 /* general-path records the Net pass deferred (device only) */,
-       ST_NECS = 11 /* top_ecs updates the DNS pass listed (device only) */, ST_WORDS = 12 };
+       ST_NECS = 11 /* top_ecs updates the DNS pass listed (device only) */,
+       ST_NECS_TCP = 12 /* DNS geo: ECS queries the TCP DNS pass listed (device only) */, ST_WORDS = 13 };
 // status allocation (zeroed per batch): the words above, padded
 #define PV_NET_THREADS 256    // pv_net_kernel: four waves
 #define PV_TRASH_WAVES 16384 // Net-pass waves with a 2-KiB trash area (grid <= 4096)
@@ -588,8 +592,30 @@ struct pv_ctx {
         // per Net slot, one exact u64 packet count per dictionary id (PV_SLOTS x dict.size());
         // cleared with the slot's Net part, summed by window folds and the multi-GPU reduce
         unsigned long long *d_cnt = nullptr;
+        // DNS v1 geo (pv_set_dns_geo): the same per DNS slot, one exact u64 per dictionary id of the
+        // ECS subnets looked up (pv_dns_ecs_geo); cleared with the slot's DNS part. Allocated at the
+        // first batch of a context that counts them.
+        unsigned long long *d_dcnt = nullptr;
         std::vector<pv_geodb::Entry> dict;
     } geo[2];
+    // DNS v1 geo (pv_set_dns_geo): the opt-in, its two filter families ([0] geoloc_notfound, [1]
+    // asn_notfound), and what the first batch builds from them (dg_setup): per family the pass byte
+    // per dictionary id (1: the string is "Unknown"), the verdict bytes per record and per TCP
+    // message, the address lists next to the top_ecs list (UDP ranks, TCP messages)
+    bool dg_on = false, dg_nf[2] = {false, false}, dg_ready = false;
+    uint8_t *d_dg_pass[2] = {nullptr, nullptr};
+    uint8_t *d_dgv = nullptr, *d_dgv_tcp = nullptr;
+    uint4 *d_ecsg = nullptr, *d_ecsg_tcp = nullptr;
+    uint64_t ecsg_cap = 0;
+    // pv_set_kernel_timing on a DNS geo context: HIP events around the DNS stage's kernels of every
+    // batch ([0] pv_dns_geo_verdict, [1] the DNS pass, [2] pv_dns_ecs, [3] pv_dns_ecs_geo; ms summed)
+    hipEvent_t dg_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    double dg_ms[4] = {0, 0, 0, 0};
+    uint64_t dg_launches = 0;
+    // a family that is set while its database is not attached filters every DNS message
+    bool dg_all() const { return dg_on && ((dg_nf[0] && !geo[0].on) || (dg_nf[1] && !geo[1].on)); }
+    bool dg_verdicts() const { return dg_on && (dg_nf[0] || dg_nf[1]) && !dg_all(); }
+    bool dg_counting() const { return dg_on && (geo[0].on || geo[1].on) && (dns_groups & PV_DNS_TOP_ECS) && !dns2_groups; }
     // Net geo filters (pv_set_net_filters): per family ([0] geoloc, [1] ASN) whether it is on, its
     // prefix list ("Unknown" for *_notfound, "<number>/" for only_asn_number), one pass byte per
     // dictionary id on the device (built at the first batch), and the per-record verdict bitmap
@@ -1002,6 +1028,9 @@ int window_slots(pv_ctx *c, const Window &w, uint32_t period, bool merged, std::
 void flush_fills(pv_ctx *c);
 int launch_fill32(pv_ctx *c, uint32_t *p, uint64_t n, uint32_t v);
 void clear_part(pv_ctx *c, int part, uint32_t s);
+// DNS v1 geo (pv_set_dns_geo): the device state its counts and filters need, built once from the
+// attached databases and the switch (first batch, or the first pv_window_regions); c->mu held
+int dg_setup(pv_ctx *c);
 void win_shift(pv_ctx *c, Window &w, int64_t T, int64_t Tns = 0);
 uint32_t host_metric(const pv_ctx *c, uint64_t key);
 const std::vector<uint64_t> &hist_points();

@@ -788,7 +788,9 @@ __device__ __forceinline__ bool dns_predicates(PV_CREF(PvParams) P, const A &R, 
 // DnsStreamHandler::_filtering, v1 (:538-648), for a message the input predicates passed: true
 // when it is filtered (process_filtered). The deep-sampling prescans use it to know which events
 // draw (a filtered one takes the manager's stale flag); it restates the filter block of
-// dns_process below, with the suffix match (0xff: no listed suffix) computed here.
+// dns_process below, with the suffix match (0xff: no listed suffix) computed here. (Not the DNS
+// geo verdict, PVDF_GEO_VERDICT: the prescans run ahead of the lists pv_dns_geo_verdict walks, so
+// the host refuses those filters with deep sampling.)
 template <class A>
 __device__ bool dns_v1_filtered(PV_CREF(PvParams) P, const A &R, uint64_t m, uint32_t dlen, uint32_t mcap, bool tcp)
 {
@@ -979,7 +981,11 @@ __device__ __forceinline__ void dns_process(PV_CREF(PvParams) P, Cache *cache, u
                     ((P.f_flags & PVDF_ANSWER_COUNT) && ancount != P.f_ancount) ||
                     ((P.f_flags & PVDF_ONLY_QUERIES) && qr) || ((P.f_flags & PVDF_ONLY_RESPONSES) && !qr) ||
                     ((P.f_flags & PVDF_ONLY_DNSSEC) && (!qr || !ancount || !dns_dnssec(R, m, dlen, qd, ancount, ns, ar))) ||
-                    (P.f_flags & PVDF_FILTER_ALL);
+                    (P.f_flags & PVDF_FILTER_ALL) ||
+                    // geoloc_notfound / asn_notfound on attached databases (:619-642, the chain's last
+                    // two checks; every check is pure, so their order decides nothing): the verdict
+                    // pv_dns_geo_verdict wrote for this record (TCP pass: this message)
+                    ((P.f_flags & PVDF_GEO_VERDICT) && P.dgv[i]);
         if (!filt && (P.f_flags & PVDF_ONLY_QTYPE)) {
             DnsInfo fd;
             dns_parse(R, m, dlen, qd, ancount, ns, ar, fd);
@@ -1121,12 +1127,25 @@ __device__ __forceinline__ void dns_process(PV_CREF(PvParams) P, Cache *cache, u
                     if (own) c.dqecs++;
                     else if (P.dns_groups & PV_DNS_COUNTERS_BIT) sum_add(P, slot, PV_OFF_DNS + DC_QECS, 1);
                     const uint64_t ek = PV_KEY(TM_ECS, fmix64(addr ^ ((uint64_t)fam << 62) ^ 0xec5ull));
-                    if constexpr (TCP || TAP) global_add(P, slot, ek, 1, i);
-                    else {
+                    if constexpr (TCP || TAP) {
+                        global_add(P, slot, ek, 1, i);
+                        if constexpr (TCP) {
+                            // DNS geo (pv_set_dns_geo): listed for pv_dns_ecs_geo (one per message at most)
+                            if (P.ecs_geo_tcp) {
+                                const uint32_t q = atomicAdd(P.n_ecs_tcp, 1u);
+                                if (q < P.ecs_tcp_cap)
+                                    reinterpret_cast<PV_G uint4 *>(P.ecs_geo_tcp)[q] = make_uint4((uint32_t)addr, (uint32_t)(addr >> 32), fam | (slot << 8), 0u);
+                                else atomicOr(P.flags, PVF_TABLE_FULL);
+                            }
+                        }
+                    } else {
                         // listed for pv_dns_ecs (one per record at most: the list holds the batch)
                         const uint32_t q = atomicAdd(P.n_ecs, 1u);
-                        if (q < P.ecs_cap) reinterpret_cast<PV_G uint4 *>(P.ecs_list)[q] = make_uint4((uint32_t)ek, (uint32_t)(ek >> 32), slot, (uint32_t)i);
-                        else atomicOr(P.flags, PVF_TABLE_FULL);
+                        if (q < P.ecs_cap) {
+                            reinterpret_cast<PV_G uint4 *>(P.ecs_list)[q] = make_uint4((uint32_t)ek, (uint32_t)(ek >> 32), slot, (uint32_t)i);
+                            // DNS geo: the address itself at the same rank, for pv_dns_ecs_geo (the key is a hash)
+                            if (P.ecs_geo) reinterpret_cast<PV_G uint4 *>(P.ecs_geo)[q] = make_uint4((uint32_t)addr, (uint32_t)(addr >> 32), fam | (slot << 8), 0u);
+                        } else atomicOr(P.flags, PVF_TABLE_FULL);
                     }
                 }
             }
@@ -5920,4 +5939,119 @@ pv_geo_verdict(const PvParams *__restrict__ Pp, PvGeoArgs G, const uint8_t *__re
     }
     const uint64_t m = __ballot(filt);
     if ((threadIdx.x & 63) == 0 && (i & ~63ull) < P.n) out[i >> 6] = m;
+}
+
+// The dictionary id of an ECS subnet as the DNS v1 handler looks it up (client_subnet as a full
+// address, libs/visor_dns/DnsAdditionalRecord.h:80-98): dns_ecs's family and address bytes
+// (little-endian in addr). IPv4: the four bytes, one step from start4. IPv6: the eight bytes the
+// reference keeps and eight zero bytes, four steps from the root; in an ip_version 4 tree: no entry.
+__device__ __forceinline__ uint32_t dns_ecs_geo_id(const PvGeoArgs &G, int k, uint32_t fam, uint64_t addr)
+{
+    uint32_t id = 0;
+    if (fam == 1) {
+        id = pv_geo_id(pv_geo_step32(G.tree[k], G.node_count[k], G.start4[k], __builtin_bswap32((uint32_t)addr)));
+    } else if (fam == 2 && G.ip_version[k] == 6) {
+        uint32_t t = G.node_count[k] ? 0u : PV_GEO_LEAF;
+        t = pv_geo_step32(G.tree[k], G.node_count[k], t, __builtin_bswap32((uint32_t)addr));
+        t = pv_geo_step32(G.tree[k], G.node_count[k], t, __builtin_bswap32((uint32_t)(addr >> 32)));
+        t = pv_geo_step32(G.tree[k], G.node_count[k], t, 0u);
+        t = pv_geo_step32(G.tree[k], G.node_count[k], t, 0u);
+        id = pv_geo_id(t);
+    }
+    return id < G.entries[k] ? id : 0u; // (a compiled tree holds no such id)
+}
+
+// top_geoLoc_ecs / top_asn_ecs of the DNS v1 handler (DnsMetricsBucket::process_dns_layer,
+// dns/v1/DnsStreamHandler.cpp:1026-1048): one lane per query the DNS pass listed for top_ecs
+// ({addr lo, addr hi, family | slot << 8, 0}; the UDP pass's list at pv_dns_ecs's ranks, or the TCP
+// pass's own), one walk per attached database, one to the DNS slot's dense count of the id (G.cnt
+// here: the DNS arrays). The adds are aggregated across the wave as pv_geo_count's are, for the
+// same reason: most subnets of real traffic share a few ids.
+extern "C" __global__ void __launch_bounds__(256)
+pv_dns_ecs_geo(const uint4 *__restrict__ list, const uint32_t *__restrict__ n_list, uint32_t cap, PvGeoArgs G)
+{
+    const uint32_t n = min(*n_list, cap);
+    const uint32_t lane = threadIdx.x & 63;
+    // (whole waves stay in the loop: the counting below votes across the wave)
+    for (uint32_t j0 = blockIdx.x * blockDim.x; j0 < n; j0 += gridDim.x * blockDim.x) {
+        const uint32_t j = j0 + threadIdx.x;
+        uint32_t fam = 0, slot = 0;
+        uint64_t addr = 0;
+        if (j < n) {
+            const uint4 e = list[j];
+            addr = (uint64_t)e.x | (uint64_t)e.y << 32;
+            fam = e.z & 0xff;
+            slot = (e.z >> 8) % PV_SLOTS; // (the pass wrote a slot; the bound costs nothing)
+            if (fam != 1 && fam != 2) fam = 0;
+        }
+        for (int k = 0; k < 2; k++) {
+            if (!G.tree[k]) continue; // (uniform)
+            const uint32_t id = fam ? dns_ecs_geo_id(G, k, fam, addr) : 0u;
+            const uint64_t word = fam ? (uint64_t)slot * G.entries[k] + id : ~0ull;
+            uint64_t todo = __ballot(fam != 0);
+            for (int r = 0; r < 4 && todo; r++) {
+                const int lead = __ffsll((unsigned long long)todo) - 1;
+                const uint64_t lw = __shfl(word, lead, 64);
+                const bool mine = fam && word == lw;
+                const uint64_t m = __ballot(mine);
+                if ((int)lane == lead) atomicAdd(&G.cnt[k][lw], (unsigned long long)__popcll(m));
+                todo &= ~m;
+            }
+            if (fam && ((todo >> lane) & 1)) atomicAdd(&G.cnt[k][word], 1ull);
+        }
+    }
+}
+
+// The DNS v1 geo filters' verdict per DNS message (DnsStreamHandler::_filtering,
+// dns/v1/DnsStreamHandler.cpp:619-642), ahead of the DNS pass, whose filter block reads it. A
+// message passes a family only when it is a query with ARCOUNT > 0 whose first additional record
+// is ECS with a non-empty subnet (dns_ecs) and the pass byte of the subnet's dictionary id is set
+// (the host set it where the entry's string equals "Unknown": no string work here). tcp == 0:
+// workgroup b walks the DNS work list of grid range b, as pv_dns_suffix does, and writes
+// out[record]; tcp != 0 (P: the TCP pass's block): one lane per message of the batch's list,
+// out[message]. A family whose pass table is null is off.
+extern "C" __global__ void __launch_bounds__(256)
+pv_dns_geo_verdict(const PvParams *__restrict__ Pp, PvGeoArgs G, const uint8_t *__restrict__ pass_city,
+                   const uint8_t *__restrict__ pass_asn, uint8_t *__restrict__ out, uint32_t out_cap, uint32_t tcp)
+{
+    PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
+    const GAcc R{P.recs};
+    uint64_t j0, j1, step;
+    if (tcp) {
+        j0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        j1 = P.tcp_nmsg;
+        step = (uint64_t)gridDim.x * blockDim.x;
+    } else {
+        const uint64_t region = (uint64_t)blockIdx.x * P.wt_per_block * PV_WT;
+        j0 = region + threadIdx.x;
+        j1 = region + min(P.dq_cnt[blockIdx.x], P.wt_per_block * (uint32_t)PV_WT);
+        step = blockDim.x;
+    }
+    for (uint64_t j = j0; j < j1; j += step) {
+        const uint4 a = reinterpret_cast<const PV_G uint4 *>(P.dq)[2 * j];
+        const uint32_t idx = a.x, mlen = a.z & 0xffff, mcap = a.z >> 16;
+        const uint64_t m = a.y;
+        if (idx >= out_cap) continue;
+        uint32_t w0, w1, w2;
+        dns_header(R, m, mcap, w0, w1, w2);
+        const uint32_t qr = (w0 >> 23) & 1;
+        const uint32_t qd = ((w1 & 0xff) << 8) | ((w1 >> 8) & 0xff);
+        const uint32_t an = ((w1 >> 8) & 0xff00) | (w1 >> 24);
+        const uint32_t ns = ((w2 & 0xff) << 8) | ((w2 >> 8) & 0xff);
+        const uint32_t ar = ((w2 >> 8) & 0xff00) | (w2 >> 24);
+        bool filt = true;
+        if (!qr && ar) {
+            uint64_t addr;
+            const uint32_t fam = dns_ecs(R, m, mlen, qd, an, ns, ar, addr);
+            if (fam) {
+                filt = false;
+                for (int k = 0; k < 2 && !filt; k++) {
+                    const uint8_t *pass = k ? pass_asn : pass_city;
+                    if (!pass) continue;
+                    if (!G.tree[k] || !pass[dns_ecs_geo_id(G, k, fam, addr)]) filt = true;
+                }
+            }
+        }
+        out[idx] = filt ? 1 : 0;
+    }
 }

@@ -322,7 +322,10 @@ enum { PVDF_EXCLUDE_NOERROR = 1, PVDF_ONLY_RCODE = 2, PVDF_ANSWER_COUNT = 4, PVD
        // (responses: rcode / answer_count / DNSSEC / qtype, queries: qname / suffix, both: the
        // transaction directions; filtered messages stay transaction events)
        PVDF_V2 = 2048, PVDF2_NOIN = 4096, PVDF2_NOOUT = 8192, PVDF2_NOUNK = 16384, PVDF2_RCODE = 32768,
-       PVDF2_QNAME = 65536 };
+       PVDF2_QNAME = 65536,
+       // DNS v1 geoloc_notfound / asn_notfound on attached databases (pv_set_dns_geo): the message's
+       // verdict byte (PvParams::dgv, written by pv_dns_geo_verdict) says whether it is filtered
+       PVDF_GEO_VERDICT = 131072 };
 // public_suffix_list table on the device (pv_host.cpp psl_blob): 512 slots of {FNV-1a of the
 // last label, byte offset, length, first suffix | count << 16}, then per suffix {offset, length}
 #define PV_PSL_SLOTS 512
@@ -505,6 +508,15 @@ struct PvParams {
     PV_G const uint32_t *psl;          // public_suffix_list table (PVDF_PSL)
     uint32_t net_contig; // diagnostic builds (-DPV_RANGE_AB, PV_NET_CONTIG=1 in the environment): lean Net workgroup b
                          // walks ranges [b * cb_fan, (b + 1) * cb_fan) instead of b, b + G, b + 2G
+    // DNS v1 geo (pv_set_dns_geo; all null without it). ecs_geo: next to ecs_list, at the same rank,
+    // what pv_dns_ecs_geo walks: {addr lo, addr hi, family | slot << 8, 0} of each listed query.
+    // The TCP pass lists into ecs_geo_tcp (n_ecs_tcp entries, at most one per message). dgv: one
+    // verdict byte per record (per message in the TCP pass), 1 = the geo filters reject it.
+    PV_G uint32_t *ecs_geo;
+    PV_G uint32_t *ecs_geo_tcp;
+    PV_G uint32_t *n_ecs_tcp; // status word
+    uint32_t ecs_tcp_cap;
+    const PV_G uint8_t *dgv;
 };
 
 // pv_fill_multi's segment list (kernel argument)

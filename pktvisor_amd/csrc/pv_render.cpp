@@ -92,7 +92,9 @@ enum { TMH_V2_IP4 = 32, TMH_V2_IP6 = 36, TMH_V2_DNS = 64 }; // DNS v2: 64 + 4 * 
 // database strings are UTF-8 text, unlike DNS names, which are raw packet bytes and stay escaped
 // byte-wise) so equal triples fold wherever names fold (window
 // merges, external buckets from contexts with other databases); geo_item splits it again.
-enum { TMH_GEO_LOC = 40, TMH_GEO_ASN = 41 };
+enum { TMH_GEO_LOC = 40, TMH_GEO_ASN = 41,
+       // the DNS v1 handler's top_geoLoc_ecs / top_asn_ecs (pv_set_dns_geo), carried the same way
+       TMH_GEO_LOC_ECS = 42, TMH_GEO_ASN_ECS = 43 };
 #define PV_GEO_SEP '\x1f'
 // (split from the right: latitude and longitude are "%f" renderings and hold no separator, so a
 // location string may hold any byte; only lists the caller marks as geo are split at all)
@@ -285,6 +287,21 @@ int load_bucket(pv_ctx *c, const std::vector<uint32_t> &slots, bool merged, int 
                 }
             }
         if (part != PART_DNS) continue;
+        for (int k = 0; k < 2; k++) {
+            // top_geoLoc_ecs / top_asn_ecs: the DNS slot's exact counts per dictionary id, by rendered string
+            const pv_ctx::GeoAttach &g = c->geo[k];
+            if (!g.d_dcnt || !c->dg_counting()) continue;
+            std::vector<uint64_t> cnt(g.dict.size());
+            if (!hip_ok(e = hipMemcpyAsync(cnt.data(), g.d_dcnt + (uint64_t)s * cnt.size(), cnt.size() * 8, hipMemcpyDeviceToHost,
+                                           c->stream)) ||
+                !hip_ok(e = hipStreamSynchronize(c->stream)))
+                return c->hipfail(e, "read DNS geo counts");
+            for (size_t i = 0; i < cnt.size(); i++) {
+                if (!cnt[i]) continue;
+                const pv_geodb::Entry &en = g.dict[i];
+                b.tops[k == 0 ? TMH_GEO_LOC_ECS : TMH_GEO_ASN_ECS][en.name + PV_GEO_SEP + en.lat + PV_GEO_SEP + en.lon] += cnt[i];
+            }
+        }
         const uint32_t sg = s | (c->gen[s] << 8);
         if (c->xq_on) continue; // (the merged view's values: after the loop, for the slot set)
         for (auto &v : c->xvals_host) {
@@ -659,9 +676,11 @@ void dns_json(pv_ctx *c, Json &j, const HostBucket &b)
     }
     if (g & PV_DNS_TOP_PORTS) top_json(j, "top_udp_ports", dense_tops(&b.sum[PV_OFF_PORT], PV_PORT_BINS, 0), topn, pct);
     if (g & PV_DNS_TOP_ECS) {
-        // geo / ASN of the subnet need a MaxMind database; none is enabled (HandlerModulePlugin::city/asn)
-        j.key("top_geoLoc_ecs").arr(); j.end_arr();
-        j.key("top_asn_ecs").arr(); j.end_arr();
+        // geo / ASN of the subnet need a MaxMind database (HandlerModulePlugin::city/asn) and the DNS
+        // geo switch (pv_set_dns_geo); without them the maps are empty (an external bucket carries
+        // what its contexts counted)
+        top_json(j, "top_geoLoc_ecs", tops_of(b, TMH_GEO_LOC_ECS), topn, pct, true);
+        top_json(j, "top_asn_ecs", tops_of(b, TMH_GEO_ASN_ECS), topn, pct, true);
         top_json(j, "top_query_ecs", tops_of(b, TM_ECS), topn, pct);
     }
     if (g & PV_DNS_TOP_QNAMES) {
@@ -1051,7 +1070,9 @@ void dns_metrics(pv_ctx *c, Sink &p, const HostBucket &b)
         p.topn("dns_top_udp_ports", "port", "Top UDP source port on the query side of a transaction", dense_tops(&b.sum[PV_OFF_PORT], PV_PORT_BINS, 0), topn, pct);
     if (g & PV_DNS_TOP_ECS) {
         if (g & PV_DNS_COUNTERS) p.gauge("dns_wire_packets_query_ecs", "Total queries that have EDNS Client Subnet (ECS) field set", d[DC_QECS]);
-        // geo / ASN of the subnet: no MaxMind database, those TopNs write nothing
+        // geo / ASN of the subnet (pv_set_dns_geo); an empty TopN writes nothing
+        p.topn("dns_top_geoLoc_ecs", "geo_loc", "Top GeoIP ECS locations", tops_of(b, TMH_GEO_LOC_ECS), topn, pct, true);
+        p.topn("dns_top_asn_ecs", "asn", "Top ASNs by ECS", tops_of(b, TMH_GEO_ASN_ECS), topn, pct, true);
         p.topn("dns_top_query_ecs", "ecs", "Top EDNS Client Subnet (ECS) observed in DNS queries", tops_of(b, TM_ECS), topn, pct);
     }
     if (g & PV_DNS_TOP_QNAMES) {

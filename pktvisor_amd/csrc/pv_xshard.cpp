@@ -958,6 +958,8 @@ int pv_window_regions(pv_ctx *c, pv_region *r, uint32_t max, uint32_t *n)
 {
     mark_merged(c, "pv_window_regions");
     std::lock_guard<std::mutex> g(c->mu);
+    // (a rank that has seen no batch lists the same regions as the others)
+    if (int rc = dg_setup(c)) return rc;
     flush_fills(c);
     std::vector<pv_region> v;
     // the parts of each slot the attached handler versions use (the others stay zero)
@@ -983,6 +985,9 @@ int pv_window_regions(pv_ctx *c, pv_region *r, uint32_t max, uint32_t *n)
         } else {
             sum(s, PV_OFF_DNS, PV_OFF_DNS2);
             cpc(s, CPC_QNAME, CPC_QNAME + 1);
+            // DNS geo (pv_set_dns_geo): the slot's top_geoLoc_ecs / top_asn_ecs counts, as the Net ones above
+            for (auto &g : c->geo)
+                if (g.d_dcnt) v.push_back(pv_region{g.d_dcnt + (size_t)s * g.dict.size(), g.dict.size(), PV_REDUCE_SUM, 0});
         }
         c->dns.clean[s] = false;
     }
