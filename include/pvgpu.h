@@ -674,9 +674,10 @@ int pv_geodb_lookup(const pv_geodb *db, const uint8_t *addrs, size_t n, uint32_t
  * combine lists), summed by window merges, external buckets (by string) and the multi-GPU
  * reduce (pv_window_regions lists them). JSON, Prometheus and OpenTelemetry carry them
  * (geo_loc with lat / lon when both exist, asn). Not built, and refused with PV_EUNSUPPORTED
- * while a database is attached: Net v2, DNS v2, pv_process_dnstap, and, unless pv_set_dns_geo
- * switched the DNS half on, the DNS top_ecs group and the DNS geoloc_notfound / asn_notfound filters. With top_ips disabled the passes still log the IP
- * entries the counts come from; the outputs then show no top_ipv4 / top_ipv6. The Net geo filters are not built either: they stay net_filter_all. */
+ * while a database is attached: pv_process_dnstap; Net v2 and DNS v2 unless pv_set_v2_geo switched
+ * them on; the DNS v1 top_ecs group and geoloc_notfound / asn_notfound filters unless
+ * pv_set_dns_geo switched that half on. With top_ips disabled the passes still log the IP entries
+ * the counts come from; the outputs then show no top_ipv4 / top_ipv6. */
 int pv_set_geodb(pv_ctx *ctx, const pv_geodb *city, const pv_geodb *asn);
 /* The Net v1 handler's geo filters, the typed form of the "geoloc_notfound", "asn_notfound",
  * "only_geoloc_prefix" and "only_asn_number" config keys (NetStreamHandler::start,
@@ -701,6 +702,58 @@ typedef struct pv_net_filters {
     const char *const *asn_numbers;  /* digit strings */
 } pv_net_filters;
 int pv_set_net_filters(pv_ctx *ctx, const pv_net_filters *f);
+/* The v2 handlers' half of the attached databases, switched on explicitly (without this call
+ * pv_set_geodb and pv_set_dns_geo keep refusing a context with Net v2 or DNS v2, and every code
+ * path, launch and output is as before). Call before the first batch and before pv_set_geodb, whose
+ * checks and allocations read it.
+ * Net v2 (NetworkMetricsBucket::process_net_layer, net/v2/NetStreamHandler.cpp:494-531,697-746):
+ * with the top_geo group, top_geo_loc_packets / top_asn_packets per direction count the address
+ * top_ipv4_packets / top_ipv6_packets count of every deep packet: in the source, out the
+ * destination, unknown both, each database independently. Exact counts per bucket, direction and
+ * dictionary id (pv_geo_count over the top-N combine lists, next to v1's). With top_ips disabled
+ * the pass still logs the IP keys the counts come from; the outputs then show no
+ * top_ipv4_packets / top_ipv6_packets.
+ * DNS v2 (DnsMetricsBucket::new_dns_transaction, dns/v2/DnsStreamHandler.cpp:1077-1088): with the
+ * top_ecs group, every counted transaction whose query carried an EDNS Client Subnet has the subnet
+ * looked up in each attached database, under the transaction's direction: top_geo_loc_ecs_xacts /
+ * top_asn_ecs_xacts. The transaction stage lists the subnets (same-batch pairs, carried queries, TCP
+ * messages and shard-edge pairs alike) and pv_dns2_ecs_geo counts them afterwards; the address rule
+ * is pv_set_dns_geo's (IPv4 four bytes, IPv6 the first eight).
+ * dns_geoloc_notfound / dns_asn_notfound (DnsStreamHandler::_filtering, :551-574) are the DNS v2
+ * handler's two geo filters: they sit in the query branch only. A query is filtered when its
+ * family's database is not attached, or it has no additional record, no ECS, or a lookup that is
+ * not exactly "Unknown" (the verdict is pv_dns_geo_verdict's, per message, UDP and TCP); a filtered
+ * query is an event and filtered_packets and still opens its transaction with the filtered flag.
+ * All of it is summed by window merges, external buckets (by string) and the multi-GPU reduce
+ * (pv_window_regions lists the arrays under the same database-hash check); JSON carries the lists
+ * (lat / lon when both exist), Prometheus and OpenTelemetry net_top_geo_loc_packets,
+ * net_top_asn_packets, dns_top_geo_loc_ecs_xacts and dns_top_asn_ecs_xacts (geo_loc with lat / lon,
+ * asn) with the direction label.
+ * Still refused with PV_EUNSUPPORTED while the switch is on: pv_process_dnstap with a database,
+ * and deep_sample_rate below 100 with a v2 geo filter, Net or DNS (sampling with only the tops is
+ * allowed). */
+typedef struct pv_v2_geo {
+    uint32_t enable;              /* nonzero: the v2 handlers read the attached databases */
+    uint32_t dns_geoloc_notfound; /* the DNS v2 handler's typed "geoloc_notfound": true */
+    uint32_t dns_asn_notfound;    /* the DNS v2 handler's typed "asn_notfound": true */
+} pv_v2_geo;
+int pv_set_v2_geo(pv_ctx *ctx, const pv_v2_geo *cfg);
+/* The Net v2 handler's own four geo filters (NetStreamHandler::start, net/v2/NetStreamHandler.cpp:
+ * 61-88; applied as _filtering :223-283): the reference's v1 and v2 Net handlers are separate
+ * instances with separate filter configs, so these have their own pass tables and verdict bitmap
+ * (pv_geo_verdict launched a second time) and do not touch v1's. Families, prefixes, the
+ * only_asn_number text and the rule for a family without its database are pv_set_net_filters'. A
+ * filtered packet is a Net v2 event (NetworkMetricsManager::process_filtered :748-753) plus
+ * filtered_packets (:486-492) and nothing else. Needs Net v2 and pv_set_v2_geo; call before the
+ * first batch, before or after pv_set_geodb; NULL clears. PV_EUNSUPPORTED with deep_sample_rate
+ * below 100 (sampling with only the v2 geo tops is allowed). */
+int pv_set_net2_filters(pv_ctx *ctx, const pv_net_filters *f);
+/* While pv_set_kernel_timing is on, a context with the v2 geo switch brackets three launches of
+ * every batch with HIP events: ms[0] the Net v2 filters' pv_geo_verdict, ms[1] pv_geo_count, which
+ * takes v1's and v2's entries in one launch, ms[2] pv_dns2_ecs_geo, summed in milliseconds over
+ * `launches` batches (a kernel that did not run adds nothing). The DNS v2 filters' pv_dns_geo_verdict
+ * is ms[0] of pv_dns_geo_timing. reset != 0 clears them. */
+int pv_v2_geo_timing(pv_ctx *ctx, double ms[3], uint64_t *launches, int reset);
 /* The DNS v1 handler's half of the attached databases, switched on explicitly (without this call
  * pv_set_geodb keeps refusing a context with the DNS top_ecs group or a DNS geo filter, and every
  * code path, launch and output is as before).
@@ -723,7 +776,7 @@ int pv_set_net_filters(pv_ctx *ctx, const pv_net_filters *f);
  * ahead of the DNS pass (pv_dns_geo_verdict: one walk per message and family, one pass byte per
  * dictionary id) and read by the pass's filter block.
  * Call before the first batch, before or after pv_set_geodb / pv_set_dns_filters; NULL clears.
- * Still refused with PV_EUNSUPPORTED: DNS v2, Net v2 and pv_process_dnstap with a database, and
+ * Still refused with PV_EUNSUPPORTED: DNS v2 and Net v2 without pv_set_v2_geo, pv_process_dnstap with a database, and
  * a DNS geo filter with deep_sample_rate below 100 (the deep-sampling prescan runs ahead of the
  * work lists the verdict is computed over, so its filter restatement cannot read it). */
 typedef struct pv_dns_geo {

@@ -72,6 +72,10 @@ class pv_dns_geo(ctypes.Structure):
     _fields_ = [("enable", ctypes.c_uint32), ("geoloc_notfound", ctypes.c_uint32), ("asn_notfound", ctypes.c_uint32)]
 
 
+class pv_v2_geo(ctypes.Structure):
+    _fields_ = [("enable", ctypes.c_uint32), ("dns_geoloc_notfound", ctypes.c_uint32), ("dns_asn_notfound", ctypes.c_uint32)]
+
+
 class pv_dhcp_config(ctypes.Structure):
     _fields_ = [("xact_ttl_ms", ctypes.c_uint32), ("recorded_stream", ctypes.c_uint32), ("max_events", ctypes.c_uint32)]
 
@@ -208,7 +212,7 @@ EXPORTS = ["pv_version", "pv_device_count", "pv_create", "pv_destroy", "pv_last_
            "pv_slow_x_finish", "pv_comm_slow_finish", "pv_geodb_open", "pv_geodb_open_file", "pv_geodb_close",
            "pv_geodb_last_error", "pv_geodb_entries", "pv_geodb_hash", "pv_geodb_hashes", "pv_set_net_filters", "pv_geodb_entry", "pv_geodb_lookup", "pv_set_geodb",
            "pv_set_dns_geo", "pv_dns_geo_timing", "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing", "pv_set_bgp", "pv_bgp_timing", "pv_chain_stats", "pv_fuse_stats",
-           "pv_ring_stats"]
+           "pv_ring_stats", "pv_set_v2_geo", "pv_set_net2_filters", "pv_v2_geo_timing"]
 PV_GEODB_CITY, PV_GEODB_ASN = 0, 1
 # pv_allreduce_fn: (uint64_t *buf, size_t n, int op, void *user) -> int
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
@@ -397,6 +401,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.pv_geodb_lookup.argtypes = [P, P, ctypes.c_size_t, U32, P]
     lib.pv_set_geodb.argtypes = [P, P, P]
     lib.pv_set_dns_geo.argtypes = [P, ctypes.POINTER(pv_dns_geo)]
+    lib.pv_set_v2_geo.argtypes = [P, ctypes.POINTER(pv_v2_geo)]
+    lib.pv_set_net2_filters.argtypes = [P, ctypes.POINTER(pv_net_filters)]
+    lib.pv_v2_geo_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     lib.pv_dns_geo_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     lib.pv_geodb_lookup_device.argtypes = [P, U32, P, ctypes.c_size_t, U32, P]
     lib.pv_set_dhcp.argtypes = [P, ctypes.POINTER(pv_dhcp_config)]
@@ -731,8 +738,13 @@ class PvHandlers:
                  deep_sample_rate: int = 100, tcp_packet_reassembly_cache_limit: int = 0, bpf=None,
                  tcp_exact_lru: bool = False, geo_city_db=None, geo_asn_db=None, dhcp_config: Optional[dict] = None,
                  dhcp_max_events: int = 0, bgp_config: Optional[dict] = None, bgp_max_events: int = 0,
-                 dns_geo: bool = False):
-        """dns_geo: the DNS v1 handler reads the attached databases too (pv_set_dns_geo): with top_ecs
+                 dns_geo: bool = False, v2_geo: bool = False):
+        """v2_geo: the v2 handlers read the attached databases (pv_set_v2_geo). Net v2: with its top_geo
+        group, top_geo_loc_packets / top_asn_packets per direction, and the four geo filter keys of
+        net2_config as the handler's own filters matched on the device (pv_set_net2_filters). DNS v2:
+        with its top_ecs group, top_geo_loc_ecs_xacts / top_asn_ecs_xacts per transaction direction,
+        and the geoloc_notfound / asn_notfound keys of dns2_config as query filters.
+        dns_geo: the DNS v1 handler reads the attached databases too (pv_set_dns_geo): with top_ecs
         enabled, top_geoLoc_ecs / top_asn_ecs of the queries' ECS subnets, and the geoloc_notfound /
         asn_notfound keys of dns_config / dns_filters as filters matched on the device.
         dhcp_config: attaches the DHCP handler ("dhcp" schema, DhcpStreamHandler) with its config
@@ -747,17 +759,20 @@ class PvHandlers:
             dgeo = filt.pop("dns_geo")
         net_filter_all = 0
         net_filters = None
+        net2_filters = None
         self.dnstap_mask = 0
         net2_groups = 0
         if net2_config is not None:
             # the Net v2 handler ("net") attached next to v1 ("packets")
-            net2_groups = pvcfg.net2_start(dict(net2_config))
+            net2_groups = pvcfg.net2_start(dict(net2_config), geo=True) if v2_geo else pvcfg.net2_start(dict(net2_config))
+            if v2_geo:
+                net2_groups, net2_filters = net2_groups["groups"], net2_groups["filters"]
         dns2_groups = 0
         if dns2_config is not None:
             # the DNS v2 handler in place of v1 (both use the "dns" schema key)
             if dns_config:
                 raise PvError("dns_config and dns2_config are exclusive: one DNS handler version")
-            d2 = pvcfg.dns2_start(dict(dns2_config))
+            d2 = pvcfg.dns2_start(dict(dns2_config), geo=True) if v2_geo else pvcfg.dns2_start(dict(dns2_config))
             dns2_groups = d2["groups"]
             filt = d2["filters"]
             self.dnstap_mask = d2["dnstap_mask"]
@@ -834,6 +849,11 @@ class PvHandlers:
             # the pcap input's config (PcapInputStream.cpp:97-99)
             self._check(self.lib.pv_set_tcp_reassembly_limit(self.ctx, int(tcp_packet_reassembly_cache_limit)),
                         "pv_set_tcp_reassembly_limit")
+        if v2_geo:
+            # first: pv_set_dns_geo's and pv_set_geodb's Net v2 refusals do not fire while it is on
+            d2geo = d2.get("v2_geo", {}) if dns2_config is not None else {}
+            g2 = pv_v2_geo(1, int(d2geo.get("geoloc_notfound", 0)), int(d2geo.get("asn_notfound", 0)))
+            self._check(self.lib.pv_set_v2_geo(self.ctx, ctypes.byref(g2)), "pv_set_v2_geo")
         if dgeo is not None:
             # before the databases: pv_set_geodb's DNS refusals do not fire while it is on
             g = pv_dns_geo(int(dgeo["enable"]), int(dgeo["geoloc_notfound"]), int(dgeo["asn_notfound"]))
@@ -847,6 +867,8 @@ class PvHandlers:
             self.set_geodb(geo_city_db, geo_asn_db)
         if net_filters:
             self.set_net_filters(**net_filters)
+        if net2_filters:
+            self.set_net_filters(v2=True, **net2_filters)
         self.dhcp_attached = False
         if dhcp is not None:
             self.set_dhcp(dhcp["xact_ttl_ms"], dhcp["recorded_stream"], dhcp_max_events)
@@ -908,9 +930,19 @@ class PvHandlers:
         self._check(self.lib.pv_ring_stats(self.ctx, out, int(reset)), "pv_ring_stats")
         return tuple(int(v) for v in out)
 
-    def set_net_filters(self, geoloc_notfound=False, asn_notfound=False, only_geoloc_prefix=None, only_asn_number=None):
-        """the Net handler's geo filters on the attached databases (pv_set_net_filters); a list of
-        None means the key is absent. Before the first batch."""
+    def v2_geo_timing(self, reset: bool = False):
+        """({kernel: ms summed}, batches) of the Net v2 geo launches, bracketed by HIP events while
+        set_kernel_timing is on, on a v2_geo context (pv_v2_geo_timing)"""
+        ms = (ctypes.c_double * 3)()
+        n = ctypes.c_uint64()
+        self._check(self.lib.pv_v2_geo_timing(self.ctx, ms, ctypes.byref(n), int(reset)), "pv_v2_geo_timing")
+        return {"pv_geo_verdict_v2": float(ms[0]), "pv_geo_count": float(ms[1]), "pv_dns2_ecs_geo": float(ms[2])}, int(n.value)
+
+    def set_net_filters(self, geoloc_notfound=False, asn_notfound=False, only_geoloc_prefix=None, only_asn_number=None,
+                        v2=False):
+        """the Net handler's geo filters on the attached databases (pv_set_net_filters; v2: the Net v2
+        handler's own, pv_set_net2_filters, on a v2_geo context); a list of None means the key is
+        absent. Before the first batch."""
         f = pv_net_filters(int(bool(geoloc_notfound)), int(bool(asn_notfound)))
         keep = []
         for name, lst in (("geoloc_prefixes", only_geoloc_prefix), ("asn_numbers", only_asn_number)):
@@ -921,6 +953,9 @@ class PvHandlers:
             setattr(f, name, ctypes.cast(arr, ctypes.POINTER(ctypes.c_char_p)))
             setattr(f, "n_" + name, len(lst))
             setattr(f, "only_geoloc_prefix_set" if name == "geoloc_prefixes" else "only_asn_number_set", 1)
+        if v2:
+            self._check(self.lib.pv_set_net2_filters(self.ctx, ctypes.byref(f)), "pv_set_net2_filters")
+            return
         self._check(self.lib.pv_set_net_filters(self.ctx, ctypes.byref(f)), "pv_set_net_filters")
 
     def set_geodb(self, city=None, asn=None):
@@ -1373,7 +1408,8 @@ def last_record_ts(recs: bytes, index: RecordIndex, ts_nano: int = 0):
 
 def pktvisor_reader(path: str, host_spec: Optional[str] = None, periods: int = 5, **kw) -> dict:
     """GPU equivalent of `pktvisor-reader [-H host_spec] --periods N FILE` for net + dns.
-    dns_geo=True (with geo_city_db / geo_asn_db): the DNS handler's half of the databases, as PvHandlers takes it."""
+    dns_geo=True (with geo_city_db / geo_asn_db): the DNS handler's half of the databases, as PvHandlers takes it.
+    v2_geo=True: the v2 handlers' half (Net v2 and DNS v2 geo tops per direction, their geo filters)."""
     linktype, ts_nano, recs = read_pcap(path)
     bpf = kw.pop("bpf", None)
     if bpf:

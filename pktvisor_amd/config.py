@@ -199,16 +199,34 @@ NET2_GROUP_DEFS = {"cardinality": 1 << 1, "counters": 1 << 0, "quantiles": 1 << 
 NET2_DEFAULT_GROUPS = ("counters", "cardinality", "quantiles", "top_geo", "top_ips")
 
 
-def net2_start(cfg: dict) -> int:
+def net2_start(cfg: dict, geo: bool = False):
     """NetStreamHandler v2 start (src/handlers/net/v2/NetStreamHandler.cpp:45-95) up to the
     signal wiring: the enabled group bits | GROUPS_SET. Its geo / ASN filters need a MaxMind
-    database and are not built for v2."""
+    database and the v2 geo switch (pv_set_v2_geo): without geo=True they raise.
+
+    geo=True: {"groups": bits | GROUPS_SET, "filters": the pv_net_filters fields or None}, the four
+    keys typed as net_start types them for v1 (:61-88); pv_set_net2_filters decides, family by
+    family, against the attached databases."""
     validate_configs(cfg, NET_CONFIG_DEFS)
     groups = process_groups(cfg, NET2_GROUP_DEFS, NET2_DEFAULT_GROUPS)
-    for k in ("geoloc_notfound", "asn_notfound", "only_geoloc_prefix", "only_asn_number"):
-        if k in cfg:
-            raise ConfigException(f"{k} is not supported by the GPU Net v2 handler")
-    return groups | GROUPS_SET
+    if not geo:
+        for k in ("geoloc_notfound", "asn_notfound", "only_geoloc_prefix", "only_asn_number"):
+            if k in cfg:
+                raise ConfigException(f"{k} is not supported by the GPU Net v2 handler")
+        return groups | GROUPS_SET
+    filters = {"geoloc_notfound": _bool(cfg, "geoloc_notfound"), "asn_notfound": _bool(cfg, "asn_notfound"),
+               "only_geoloc_prefix": None, "only_asn_number": None}
+    if "only_geoloc_prefix" in cfg:
+        filters["only_geoloc_prefix"] = list(_string_list(cfg, "only_geoloc_prefix"))
+    if "only_asn_number" in cfg:
+        numbers = list(_string_list(cfg, "only_asn_number"))
+        for number in numbers:
+            if not number.isdigit():
+                raise ConfigException(f"NetStreamHandler: only_asn_number filter contained an invalid/unsupported value: {number}")
+        filters["only_asn_number"] = numbers
+    on = filters["geoloc_notfound"] or filters["asn_notfound"] or filters["only_geoloc_prefix"] is not None \
+        or filters["only_asn_number"] is not None
+    return {"groups": groups | GROUPS_SET, "filters": filters if on else None}
 
 
 # DNS v2 (src/handlers/dns/v2/DnsStreamHandler.h:40-52,549-575; defaults .cpp:51-57)
@@ -223,17 +241,21 @@ DNS2_FILTER_KEYS = ("exclude_noerror", "only_rcode", "only_dnssec_response", "an
                     "only_qname_suffix")
 
 
-def dns2_start(cfg: dict) -> dict:
+def dns2_start(cfg: dict, geo: bool = False) -> dict:
     """DnsStreamHandler v2 start (src/handlers/dns/v2/DnsStreamHandler.cpp:43-236) up to the
     signal wiring: {"groups": bits | GROUPS_SET, "filters": pv_dns_filters fields (v2) or None,
     "xact_ttl_ms": int|None}. The geo / ASN filters (no MaxMind database) are not built for the
     GPU v2 handler; top_ecs keeps
-    its geo / ASN tops empty (no MaxMind database)."""
+    its geo / ASN tops empty (no MaxMind database).
+
+    geo=True (the v2 geo switch, pv_set_v2_geo): geoloc_notfound / asn_notfound do not raise and
+    come back typed under "v2_geo" (the pv_v2_geo dns_* fields): query-branch filters matched on the
+    device against the attached databases (dns/v2/DnsStreamHandler.cpp:551-574)."""
     from pktvisor_amd import dns_filter_config
     validate_configs(cfg, DNS2_CONFIG_DEFS)
     groups = process_groups(cfg, DNS2_GROUP_DEFS, DNS2_DEFAULT_GROUPS)
     for k in ("geoloc_notfound", "asn_notfound"):
-        if k in cfg:
+        if k in cfg and not geo:
             raise ConfigException(f"{k} is not supported by the GPU DNS v2 handler")
     # dnstap_msg_type (dns/v2/DnsStreamHandler.cpp:176-190): as v1's
     if "dnstap_msg_type" in cfg and cfg["dnstap_msg_type"] not in DNSTAP_MSG_TYPES:
@@ -263,7 +285,10 @@ def dns2_start(cfg: dict) -> dict:
         ttl = _uint(cfg, "xact_ttl_ms")
     elif "xact_ttl_secs" in cfg:
         ttl = _uint(cfg, "xact_ttl_secs") * 1000
-    return {"groups": groups | GROUPS_SET, "filters": filters, "xact_ttl_ms": ttl, "dnstap_mask": mask}
+    out = {"groups": groups | GROUPS_SET, "filters": filters, "xact_ttl_ms": ttl, "dnstap_mask": mask}
+    if geo:
+        out["v2_geo"] = {"geoloc_notfound": _bool(cfg, "geoloc_notfound"), "asn_notfound": _bool(cfg, "asn_notfound")}
+    return out
 
 
 def dns_start(cfg: dict, dns_geo: bool = False) -> dict:

@@ -39,6 +39,9 @@ PV_GEO_HD inline uint32_t pv_geo_id(uint32_t w) { return (w & PV_GEO_LEAF) ? (w 
 struct PvGeoArgs {
     const uint32_t *tree[2];
     unsigned long long *cnt[2]; // PV_SLOTS x entries: packets per Net slot and dictionary id
+    // Net v2 (pv_set_v2_geo): PV_SLOTS x 3 x entries, packets per Net slot, direction and dictionary
+    // id; null: the v2 handler does not count. (cnt is null likewise while v1's top_geo is off.)
+    unsigned long long *cnt2[2];
     uint32_t node_count[2], start4[2], ip_version[2], entries[2];
 };
 

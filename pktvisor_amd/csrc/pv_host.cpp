@@ -123,11 +123,15 @@ void clear_part(pv_ctx *c, int part, uint32_t s)
         launch_fill64(c, cpc, PV_MIN_NET_WORDS, (uint64_t)PV_CPC_EMPTY);
         for (auto &g : c->geo)
             if (g.d_cnt) launch_fill64(c, (uint64_t *)g.d_cnt + (uint64_t)s * g.dict.size(), g.dict.size(), 0);
+        for (auto &g : c->geo)
+            if (g.d_cnt2) launch_fill64(c, (uint64_t *)g.d_cnt2 + (uint64_t)s * 3 * g.dict.size(), 3 * g.dict.size(), 0);
     } else {
         launch_fill64(c, sum + PV_OFF_DNS, PV_SUM_WORDS - PV_OFF_DNS, 0);
         launch_fill64(c, cpc + PV_MIN_NET_WORDS, PV_MIN_WORDS - PV_MIN_NET_WORDS, (uint64_t)PV_CPC_EMPTY);
         for (auto &g : c->geo)
             if (g.d_dcnt) launch_fill64(c, (uint64_t *)g.d_dcnt + (uint64_t)s * g.dict.size(), g.dict.size(), 0);
+        for (auto &g : c->geo)
+            if (g.d_dcnt2) launch_fill64(c, (uint64_t *)g.d_dcnt2 + (uint64_t)s * 3 * g.dict.size(), 3 * g.dict.size(), 0);
     }
     // keys only: a count or name word is read only behind a non-zero key, and whoever
     // claims an entry overwrites its name word and adds net of the stale count (global_add,
@@ -317,6 +321,8 @@ int pv_set_tcp_exact_lru(pv_ctx *c, int on)
 }
 
 static int nf_build(pv_ctx *c);
+static int nf2_build(pv_ctx *c);
+static int nf_parse(pv_ctx *c, const pv_net_filters *f, bool on[2], std::vector<std::string> pre[2]);
 int pv_set_geodb(pv_ctx *c, const pv_geodb *city, const pv_geodb *asn)
 {
     if (!c) return PV_EINVAL;
@@ -328,8 +334,9 @@ int pv_set_geodb(pv_ctx *c, const pv_geodb *city, const pv_geodb *asn)
             return c->fail(PV_EINVAL, "pv_set_geodb: the %s database was opened as the other kind", k ? "ASN" : "city");
     if (city || asn) {
         // what a database would have to feed and does not yet: refused, not approximated
-        if (c->net2_groups) return c->fail(PV_EUNSUPPORTED, "geo databases: the Net v2 handler's top_geo is not built");
-        if (c->dns2_groups) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS v2 handler's geo metrics are not built");
+        // (the v2 handlers are opt-in, pv_set_v2_geo: without it both stay refused)
+        if (c->net2_groups && !c->v2g_on) return c->fail(PV_EUNSUPPORTED, "geo databases: the Net v2 handler's top_geo is not built");
+        if (c->dns2_groups && !c->v2g_on) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS v2 handler's geo metrics are not built");
         // (the DNS v1 half is opt-in, pv_set_dns_geo: without it both stay refused)
         if (!c->dg_on && (c->dns_groups & PV_DNS_TOP_ECS))
             return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS top_ecs group's geo metrics are not built");
@@ -344,16 +351,21 @@ int pv_set_geodb(pv_ctx *c, const pv_geodb *city, const pv_geodb *asn)
         if (g.d_tree) hipFree(g.d_tree);
         if (g.d_cnt) hipFree(g.d_cnt);
         if (g.d_dcnt) hipFree(g.d_dcnt);
+        if (g.d_cnt2) hipFree(g.d_cnt2);
+        if (g.d_dcnt2) hipFree(g.d_dcnt2);
         g = pv_ctx::GeoAttach();
     };
     for (uint32_t k = 0; k < 2; k++) {
         if (!dbs[k]) continue;
         pv_ctx::GeoAttach &g = next[k];
         const size_t bytes = dbs[k]->tree.size() * 4, cbytes = (size_t)PV_SLOTS * dbs[k]->dict.size() * 8;
+        // (Net v2 geo: a count per direction too, only where the v2 handler counts)
+        const bool v2 = c->v2g_on && (c->net2_groups & PV_N2G_TOP_GEO);
         // (an empty tree still gets a word, so the kernel's pointer is never null)
         if (!hip_ok(e = hipMalloc(&g.d_tree, std::max<size_t>(bytes, 8))) ||
             (bytes && !hip_ok(e = hipMemcpy(g.d_tree, dbs[k]->tree.data(), bytes, hipMemcpyHostToDevice))) ||
-            !hip_ok(e = hipMalloc(&g.d_cnt, cbytes)) || !hip_ok(e = hipMemset(g.d_cnt, 0, cbytes))) {
+            !hip_ok(e = hipMalloc(&g.d_cnt, cbytes)) || !hip_ok(e = hipMemset(g.d_cnt, 0, cbytes)) ||
+            (v2 && (!hip_ok(e = hipMalloc(&g.d_cnt2, 3 * cbytes)) || !hip_ok(e = hipMemset(g.d_cnt2, 0, 3 * cbytes))))) {
             drop(next[0]);
             drop(next[1]);
             return c->hipfail(e, "geo database tree and counts");
@@ -374,39 +386,44 @@ int pv_set_geodb(pv_ctx *c, const pv_geodb *city, const pv_geodb *asn)
         c->d_dg_pass[k] = nullptr;
     }
     c->dg_ready = false;
-    return nf_build(c); // (filters set earlier match the new dictionaries)
+    if (int rc = nf_build(c)) return rc; // (filters set earlier match the new dictionaries)
+    return nf2_build(c);
 }
 
-// The pass tables of the geo filters: per family one byte per dictionary id, 1 where a configured
-// prefix is a prefix of the id's string (begins_with, net/v1/NetStreamHandler.cpp:218-221).
+// The pass tables of a Net handler's geo filters: per family one byte per dictionary id, 1 where a
+// configured prefix is a prefix of the id's string (begins_with, net/v1/NetStreamHandler.cpp:218-221),
+// and the per-record verdict bitmap. One body for v1's members and for Net v2's own.
 // Called with c->mu held, whenever the databases or the filters change.
-static int nf_build(pv_ctx *c)
+static int nf_build_for(pv_ctx *c, bool verdicts, const bool on[2], const std::vector<std::string> prefix[2], uint8_t *d_pass[2],
+                        unsigned long long *&d_bitmap)
 {
     hipError_t e = hipSetDevice(c->device);
     for (int k = 0; k < 2; k++) {
-        if (c->d_nf_pass[k]) hipFree(c->d_nf_pass[k]);
-        c->d_nf_pass[k] = nullptr;
+        if (d_pass[k]) hipFree(d_pass[k]);
+        d_pass[k] = nullptr;
     }
-    if (!c->nf_verdicts()) return 0;
+    if (!verdicts) return 0;
     for (int k = 0; k < 2; k++) {
-        if (!c->nf_on[k]) continue;
+        if (!on[k]) continue;
         const auto &dict = c->geo[k].dict;
         std::vector<uint8_t> pass(dict.size(), 0);
         for (size_t i = 0; i < dict.size(); i++)
-            for (const std::string &pre : c->nf_prefix[k])
+            for (const std::string &pre : prefix[k])
                 if (dict[i].name.size() >= pre.size() && !dict[i].name.compare(0, pre.size(), pre)) { pass[i] = 1; break; }
-        if (!hip_ok(e = hipMalloc(&c->d_nf_pass[k], pass.size())) ||
-            !hip_ok(e = hipMemcpy(c->d_nf_pass[k], pass.data(), pass.size(), hipMemcpyHostToDevice)))
+        if (!hip_ok(e = hipMalloc(&d_pass[k], std::max<size_t>(pass.size(), 1))) ||
+            !hip_ok(e = hipMemcpy(d_pass[k], pass.data(), pass.size(), hipMemcpyHostToDevice)))
             return c->hipfail(e, "geo filter pass table");
     }
-    if (!c->d_gfilt) {
+    if (!d_bitmap) {
         // (one bit a record, padded so a wave past the span's end writes and reads in bounds)
         const size_t words = (size_t)(c->max_records / 64 + 8);
-        if (!hip_ok(e = hipMalloc(&c->d_gfilt, words * 8)) || !hip_ok(e = hipMemset(c->d_gfilt, 0, words * 8)))
+        if (!hip_ok(e = hipMalloc(&d_bitmap, words * 8)) || !hip_ok(e = hipMemset(d_bitmap, 0, words * 8)))
             return c->hipfail(e, "geo filter verdicts");
     }
     return 0;
 }
+static int nf_build(pv_ctx *c) { return nf_build_for(c, c->nf_verdicts(), c->nf_on, c->nf_prefix, c->d_nf_pass, c->d_gfilt); }
+static int nf2_build(pv_ctx *c) { return nf_build_for(c, c->nf2_verdicts(), c->nf2_on, c->nf2_prefix, c->d_nf2_pass, c->d_gfilt2); }
 
 int pv_set_net_filters(pv_ctx *c, const pv_net_filters *f)
 {
@@ -415,28 +432,96 @@ int pv_set_net_filters(pv_ctx *c, const pv_net_filters *f)
     if (c->records_seen) return c->fail(PV_EINVAL, "Net filters must be set before the first batch");
     bool on[2] = {false, false};
     std::vector<std::string> pre[2];
-    if (f) {
-        // NetStreamHandler::start's filter setup (net/v1/NetStreamHandler.cpp:61-88)
-        if (f->geoloc_notfound) { on[0] = true; pre[0].push_back("Unknown"); }
-        if (f->asn_notfound) { on[1] = true; pre[1].push_back("Unknown"); }
-        if (f->only_geoloc_prefix_set) {
-            on[0] = true;
-            for (uint32_t i = 0; i < f->n_geoloc_prefixes; i++) pre[0].push_back(f->geoloc_prefixes[i] ? f->geoloc_prefixes[i] : "");
-        }
-        if (f->only_asn_number_set) {
-            on[1] = true;
-            for (uint32_t i = 0; i < f->n_asn_numbers; i++) {
-                const std::string n = f->asn_numbers[i] ? f->asn_numbers[i] : "";
-                if (!std::all_of(n.begin(), n.end(), [](unsigned char ch) { return std::isdigit(ch); }))
-                    return c->fail(PV_EINVAL, "NetStreamHandler: only_asn_number filter contained an invalid/unsupported value: %s", n.c_str());
-                pre[1].push_back(n + "/");
-            }
-        }
-    }
+    // NetStreamHandler::start's filter setup (net/v1/NetStreamHandler.cpp:61-88)
+    if (int rc = nf_parse(c, f, on, pre)) return rc;
     if ((on[0] || on[1]) && c->sample_rate < 100)
         return c->fail(PV_EUNSUPPORTED, "deep_sample_rate below 100 with geo filters is not built");
     for (int k = 0; k < 2; k++) { c->nf_on[k] = on[k]; c->nf_prefix[k] = pre[k]; }
     return nf_build(c);
+}
+
+// pv_set_net_filters' parse of the four keys into the two families (NetStreamHandler::start; v1
+// net/v1/NetStreamHandler.cpp:61-88 and v2 net/v2/NetStreamHandler.cpp:61-88 read alike)
+static int nf_parse(pv_ctx *c, const pv_net_filters *f, bool on[2], std::vector<std::string> pre[2])
+{
+    if (!f) return 0;
+    if (f->geoloc_notfound) { on[0] = true; pre[0].push_back("Unknown"); }
+    if (f->asn_notfound) { on[1] = true; pre[1].push_back("Unknown"); }
+    if (f->only_geoloc_prefix_set) {
+        on[0] = true;
+        for (uint32_t i = 0; i < f->n_geoloc_prefixes; i++) pre[0].push_back(f->geoloc_prefixes[i] ? f->geoloc_prefixes[i] : "");
+    }
+    if (f->only_asn_number_set) {
+        on[1] = true;
+        for (uint32_t i = 0; i < f->n_asn_numbers; i++) {
+            const std::string n = f->asn_numbers[i] ? f->asn_numbers[i] : "";
+            if (!std::all_of(n.begin(), n.end(), [](unsigned char ch) { return std::isdigit(ch); }))
+                return c->fail(PV_EINVAL, "NetStreamHandler: only_asn_number filter contained an invalid/unsupported value: %s", n.c_str());
+            pre[1].push_back(n + "/");
+        }
+    }
+    return 0;
+}
+
+int pv_set_v2_geo(pv_ctx *c, const pv_v2_geo *cfg)
+{
+    if (!c) return PV_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->records_seen) return c->fail(PV_EINVAL, "the v2 geo switch must be set before the first batch");
+    if (c->geo[0].on || c->geo[1].on) return c->fail(PV_EINVAL, "the v2 geo switch must be set before pv_set_geodb");
+    const bool on = cfg && cfg->enable;
+    const bool dnf[2] = {on && cfg->dns_geoloc_notfound, on && cfg->dns_asn_notfound};
+    if ((dnf[0] || dnf[1]) && !c->dns2_groups)
+        return c->fail(PV_EINVAL, "v2 geo: dns_geoloc_notfound / dns_asn_notfound are the DNS v2 handler's filters (DNS v1: pv_set_dns_geo)");
+    // (the deep-sampling prescan restates the v2 filter chain ahead of the work lists the verdict is computed over)
+    if ((dnf[0] || dnf[1]) && c->sample_rate < 100)
+        return c->fail(PV_EUNSUPPORTED, "deep_sample_rate below 100 with DNS v2 geo filters is not built");
+    if (!on && (c->nf2_on[0] || c->nf2_on[1]))
+        return c->fail(PV_EINVAL, "the Net v2 geo filters need the v2 geo switch");
+    c->v2g_on = on;
+    if (c->dns2_groups) {
+        // the DNS v2 handler's two filters use the verdict machinery of pv_set_dns_geo (dg_setup builds
+        // the pass tables and verdict bytes, pv_dns_geo_verdict runs ahead of the DNS pass); the v2
+        // filter block of dns_process consults the byte for queries only
+        c->dg_on = dnf[0] || dnf[1];
+        c->dg_nf[0] = dnf[0];
+        c->dg_nf[1] = dnf[1];
+        c->dg_ready = false;
+    }
+    if (on) {
+        hipError_t e = hipSetDevice(c->device);
+        for (auto &ev : c->v2g_ev)
+            if (!ev && !hip_ok(e = hipEventCreate(&ev))) return c->hipfail(e, "v2 geo timing events");
+    }
+    return 0;
+}
+
+int pv_v2_geo_timing(pv_ctx *c, double ms[3], uint64_t *launches, int reset)
+{
+    if (!c) return PV_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int k = 0; k < 3 && ms; k++) ms[k] = c->v2g_ms[k];
+    if (launches) *launches = c->v2g_launches;
+    if (reset) { c->v2g_ms[0] = c->v2g_ms[1] = c->v2g_ms[2] = 0; c->v2g_launches = 0; }
+    return 0;
+}
+
+int pv_set_net2_filters(pv_ctx *c, const pv_net_filters *f)
+{
+    if (!c) return PV_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->records_seen) return c->fail(PV_EINVAL, "Net v2 filters must be set before the first batch");
+    bool on[2] = {false, false};
+    std::vector<std::string> pre[2];
+    // NetStreamHandler::start's filter setup (net/v2/NetStreamHandler.cpp:61-88)
+    if (int rc = nf_parse(c, f, on, pre)) return rc;
+    if ((on[0] || on[1]) && !(c->v2g_on && c->net2_groups))
+        return c->fail(PV_EUNSUPPORTED, "Net v2 geo filters need the Net v2 handler and the v2 geo switch (pv_set_v2_geo)");
+    // (as for v1: the verdict is not known when the deep-sampling draws are laid out)
+    if ((on[0] || on[1]) && c->sample_rate < 100)
+        return c->fail(PV_EUNSUPPORTED, "deep_sample_rate below 100 with Net v2 geo filters is not built");
+    for (int k = 0; k < 2; k++) { c->nf2_on[k] = on[k]; c->nf2_prefix[k] = pre[k]; }
+    return nf2_build(c);
 }
 
 int pv_set_dns_geo(pv_ctx *c, const pv_dns_geo *cfg)
@@ -447,8 +532,8 @@ int pv_set_dns_geo(pv_ctx *c, const pv_dns_geo *cfg)
     const bool on = cfg && cfg->enable;
     const bool nf[2] = {on && cfg->geoloc_notfound, on && cfg->asn_notfound};
     if (on && (c->geo[0].on || c->geo[1].on)) {
-        if (c->net2_groups) return c->fail(PV_EUNSUPPORTED, "geo databases: the Net v2 handler's top_geo is not built");
-        if (c->dns2_groups) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS v2 handler's geo metrics are not built");
+        if (c->net2_groups && !c->v2g_on) return c->fail(PV_EUNSUPPORTED, "geo databases: the Net v2 handler's top_geo is not built");
+        if (c->dns2_groups && !c->v2g_on) return c->fail(PV_EUNSUPPORTED, "geo databases: the DNS v2 handler's geo metrics are not built");
     }
     if (on && c->dns2_groups && (nf[0] || nf[1]))
         return c->fail(PV_EUNSUPPORTED, "geoloc_notfound / asn_notfound are not DNS v2 filters here");
@@ -504,6 +589,60 @@ extern "C++" int pvh::dg_setup(pv_ctx *c)
         if (!ev && !hip_ok(e = hipEventCreate(&ev))) return c->hipfail(e, "DNS geo timing events");
     c->dg_ready = true;
     return 0;
+}
+
+// DNS v2 geo (pv_set_v2_geo): what a launch that reaches dns2_xact needs. The [DNS slot][xd][id]
+// counts are allocated at the first such launch of a context that counts them; the list grows to the
+// launch's bound (one rank per counted transaction, at most one per event or edge pair), so a
+// steady-state batch allocates nothing.
+extern "C++" int pvh::v2g_setup(pv_ctx *c)
+{
+    if (!c->dns2_geo_counting()) return 0;
+    hipError_t e = hipSetDevice(c->device);
+    for (auto &g : c->geo) {
+        if (!g.on || g.d_dcnt2) continue;
+        const size_t cbytes = (size_t)PV_SLOTS * 3 * g.dict.size() * 8;
+        if (!hip_ok(e = hipMalloc(&g.d_dcnt2, cbytes)) || !hip_ok(e = hipMemset(g.d_dcnt2, 0, cbytes)))
+            return c->hipfail(e, "DNS v2 geo counts");
+    }
+    return 0;
+}
+extern "C++" int pvh::v2g_list(pv_ctx *c, uint64_t need, PvXactParams &X, hipStream_t st)
+{
+    if (!c->dns2_geo_counting()) return 0;
+    hipError_t e = hipSuccess;
+    if (int rc = v2g_setup(c)) return rc;
+    if (!c->d_g2n && !hip_ok(e = hipMalloc(&c->d_g2n, 64))) return c->hipfail(e, "DNS v2 geo list count");
+    if (c->g2_cap < need || !c->d_g2list) {
+        if (c->d_g2list) { hipStreamSynchronize(st); hipFree(c->d_g2list); }
+        c->d_g2list = nullptr;
+        c->g2_cap = 0;
+        const uint64_t cap = std::max<uint64_t>(need, 1024);
+        if (!hip_ok(e = hipMalloc(&c->d_g2list, cap * sizeof(uint4)))) return c->hipfail(e, "DNS v2 geo list");
+        c->g2_cap = cap;
+    }
+    if (!hip_ok(e = hipMemsetAsync(c->d_g2n, 0, 4, st))) return c->hipfail(e, "DNS v2 geo list count");
+    X.geo2_list = reinterpret_cast<uint32_t *>(c->d_g2list);
+    X.n_geo2 = c->d_g2n;
+    X.geo2_cap = (uint32_t)std::min<uint64_t>(c->g2_cap, 0xffffffffu);
+    return 0;
+}
+extern "C++" void pvh::v2g_count(pv_ctx *c, hipStream_t st)
+{
+    if (!c->dns2_geo_counting() || !c->d_g2list) return;
+    PvGeoArgs G{};
+    for (int k = 0; k < 2; k++) {
+        const pv_ctx::GeoAttach &g = c->geo[k];
+        if (!g.on || !g.d_dcnt2) continue;
+        G.tree[k] = g.d_tree;
+        G.cnt[k] = g.d_dcnt2;
+        G.node_count[k] = g.node_count;
+        G.start4[k] = g.start4;
+        G.ip_version[k] = g.ip_version;
+        G.entries[k] = (uint32_t)g.dict.size();
+    }
+    hipLaunchKernelGGL(pv_dns2_ecs_geo, dim3((uint32_t)c->cus * 2), dim3(256), 0, st, (const uint4 *)c->d_g2list,
+                       (const uint32_t *)c->d_g2n, (uint32_t)std::min<uint64_t>(c->g2_cap, 0xffffffffu), G);
 }
 
 int pv_dns_geo_timing(pv_ctx *c, double ms[4], uint64_t *launches, int reset)
@@ -891,14 +1030,21 @@ void pv_destroy(pv_ctx *c)
     dhcp_free(c);
     bgp_free(c);
     for (void *p : {(void *)c->d_nf_pass[0], (void *)c->d_nf_pass[1], (void *)c->d_gfilt}) if (p) hipFree(p);
+    for (void *p : {(void *)c->d_nf2_pass[0], (void *)c->d_nf2_pass[1], (void *)c->d_gfilt2}) if (p) hipFree(p);
     for (auto &g : c->geo) {
         if (g.d_tree) hipFree(g.d_tree);
         if (g.d_cnt) hipFree(g.d_cnt);
         if (g.d_dcnt) hipFree(g.d_dcnt);
+        if (g.d_cnt2) hipFree(g.d_cnt2);
+        if (g.d_dcnt2) hipFree(g.d_dcnt2);
     }
     for (void *p : {(void *)c->d_dg_pass[0], (void *)c->d_dg_pass[1], (void *)c->d_dgv, (void *)c->d_dgv_tcp, (void *)c->d_ecsg,
                     (void *)c->d_ecsg_tcp})
         if (p) hipFree(p);
+    if (c->d_g2list) hipFree(c->d_g2list);
+    if (c->d_g2n) hipFree(c->d_g2n);
+    for (hipEvent_t ev : c->v2g_ev)
+        if (ev) hipEventDestroy(ev);
     for (hipEvent_t ev : c->dg_ev)
         if (ev) hipEventDestroy(ev);
     if (c->d_dbits) hipFree(c->d_dbits);
@@ -1169,14 +1315,18 @@ void params_common(pv_ctx *c, PvParams &P, const uint8_t *d_recs, const uint32_t
     P.ts_nano = c->cfg.ts_nano;
     P.net_groups = c->dev_net_groups();
     P.dns_groups = c->dns_groups;
-    P.net2_groups = c->net2_groups;
+    P.net2_groups = c->dev_net2_groups();
     P.dns2_groups = c->dns2_groups;
     P.net_filter_all = (c->cfg.net_filter_all || c->nf_all()) ? 1u : 0u;
     P.gfilt = c->nf_verdicts() ? (const uint64_t *)c->d_gfilt : nullptr;
+    P.net2_filter_all = c->nf2_all() ? 1u : 0u;
+    P.gfilt2 = c->nf2_verdicts() ? (const uint64_t *)c->d_gfilt2 : nullptr;
     P.nets = c->nets;
     // (DNS geo filters, pv_set_dns_geo: a family without its database filters every message; else
     // the verdict bytes pv_dns_geo_verdict writes ahead of the DNS pass)
     P.f_flags = c->f_flags | (c->dg_all() ? (uint32_t)PVDF_FILTER_ALL : 0u) | (c->dg_verdicts() ? (uint32_t)PVDF_GEO_VERDICT : 0u);
+    // (DNS v2, pv_set_v2_geo: the same two bits, read by the v2 filter block, which PVDF_V2 selects)
+    if (c->dns2_groups && (c->dg_all() || c->dg_verdicts())) P.f_flags |= PVDF_V2;
     P.dgv = c->dg_verdicts() ? c->d_dgv : nullptr;
     P.f_rcode_mask = c->f_rcode_mask;
     P.f_ancount = c->f_ancount;
@@ -2070,6 +2220,9 @@ int pair_stage(pv_ctx *c, const PvParams &P, uint32_t nev_b, uint32_t nkeys, uin
         X.edge_h = c->slow_defer ? c->edge_h : 0;
         X.orph_ord = c->slow_defer && c->dns2_groups ? c->d_orph_ord : nullptr; // DNS v2 stubs
         HP(15);
+        // DNS v2 geo: the transactions this launch counts in top_ecs, listed (at most one per event)
+        if (P.dns2_groups)
+            if (int rc = v2g_list(c, nev, X, st)) return rc;
         if (!hip_ok(e = hipMemsetAsync(c->d_nvals + 2, 0, 4, st))) return c->hipfail(e, "parameter upload");
         HP(16);
         if (!hip_ok(e = (*c->h_xparams = X, upload_params(c->d_xparams, c->h_xparams, sizeof X, st))))
@@ -2082,6 +2235,17 @@ int pair_stage(pv_ctx *c, const PvParams &P, uint32_t nev_b, uint32_t nkeys, uin
         hipLaunchKernelGGL(P.dns2_groups ? pv_xact_resolve2 : pv_xact_resolve, dim3(blocks), dim3(threads), rpad, st,
                            (const PvXactParams *)c->d_xparams);
         if (!hip_ok(e = hipGetLastError())) return c->hipfail(e, "launch pv_xact_resolve");
+        // DNS v2 geo: top_geo_loc_ecs_xacts / top_asn_ecs_xacts of the transactions just listed
+        if (X.geo2_list) {
+            // (pv_set_kernel_timing: events around the count kernel, waited for here on timed batches only)
+            const bool timed = c->timing_every && c->v2g_ev[5];
+            if (timed) hipEventRecord(c->v2g_ev[4], st);
+            v2g_count(c, st);
+            float ms;
+            if (timed && hipEventRecord(c->v2g_ev[5], st) == hipSuccess && hipEventSynchronize(c->v2g_ev[5]) == hipSuccess &&
+                hipEventElapsedTime(&ms, c->v2g_ev[4], c->v2g_ev[5]) == hipSuccess)
+                c->v2g_ms[2] += ms;
+        }
         HP(18);
         // (the resolve kernel also moves the queries still open to the carried list: pv_xact_carry's work)
         // the DNS v1 resolve lists the slow transactions of periods with a threshold for
@@ -2222,6 +2386,7 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     // and the transaction stage as any span's do.
     const uint64_t nord = n ? n : 1;
     if (int rc = dg_setup(c)) return rc;
+    if (int rc = v2g_setup(c)) return rc;
     PvParams P;
     params_common(c, P, d_recs, d_offs, n);
     // a batch with no TCP stage ahead of it is one span: its Net pass emits the TCP segments
@@ -2468,9 +2633,9 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
     // at their first line. The guess cannot change a result: the combine reads the Net pass's two
     // counts and leaves a batch that has either untouched, and the regular chain then runs from
     // pv_net_slow_list on (below, after the read-back). Not with Net v2 (its pass sits between), nor
-    // with geo counting (pv_geo_count reads the combine's lists). PV_PLAIN_CHAIN=0 keeps every
+    // with geo counting, v1's or Net v2's (pv_geo_count reads the combine's lists). PV_PLAIN_CHAIN=0 keeps every
     // batch on the regular chain.
-    bool plain = lean && !(force && !strcmp(force, "span")) && c->cb_plain && !c->net2_groups && !c->geo_counting();
+    bool plain = lean && !(force && !strcmp(force, "span")) && c->cb_plain && !c->net2_groups && !c->geo_counting() && !c->geo2_counting();
     if (plain) {
         const char *pc = getenv("PV_PLAIN_CHAIN");
         if (pc && atoi(pc) == 0) plain = false;
@@ -2559,7 +2724,10 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         const char *fr = getenv("PV_FUSE_RING");
         if (fr && atoi(fr) == 0) ring = false;
     }
-    if (P.gfilt && n) {
+    // (pv_set_kernel_timing on a v2 geo context: events around the v2 verdict launch and pv_geo_count)
+    const bool v2g_timed = c->timing_every && c->v2g_on && c->v2g_ev[3];
+    bool v2g_stamped[2] = {false, false};
+    if ((P.gfilt || P.gfilt2) && n) {
         // the geo filters' verdict of every record of the span, for the general pass to read
         PvGeoArgs G{};
         for (int k = 0; k < 2; k++) {
@@ -2571,9 +2739,17 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
             G.ip_version[k] = g.ip_version;
             G.entries[k] = (uint32_t)g.dict.size();
         }
-        hipLaunchKernelGGL(pv_geo_verdict, dim3((uint32_t)((P.n + 255) / 256)), dim3(256), 0, st, dp, G,
-                           (const uint8_t *)(c->nf_on[0] ? c->d_nf_pass[0] : nullptr),
-                           (const uint8_t *)(c->nf_on[1] ? c->d_nf_pass[1] : nullptr), c->d_gfilt);
+        if (P.gfilt)
+            hipLaunchKernelGGL(pv_geo_verdict, dim3((uint32_t)((P.n + 255) / 256)), dim3(256), 0, st, dp, G,
+                               (const uint8_t *)(c->nf_on[0] ? c->d_nf_pass[0] : nullptr),
+                               (const uint8_t *)(c->nf_on[1] ? c->d_nf_pass[1] : nullptr), c->d_gfilt);
+        // the Net v2 handler's own filters: the same kernel on its pass tables, for pv_net2_kernel
+        if (P.gfilt2 && v2g_timed) { hipEventRecord(c->v2g_ev[0], st); v2g_stamped[0] = true; }
+        if (P.gfilt2)
+            hipLaunchKernelGGL(pv_geo_verdict, dim3((uint32_t)((P.n + 255) / 256)), dim3(256), 0, st, dp, G,
+                               (const uint8_t *)(c->nf2_on[0] ? c->d_nf2_pass[0] : nullptr),
+                               (const uint8_t *)(c->nf2_on[1] ? c->d_nf2_pass[1] : nullptr), c->d_gfilt2);
+        if (v2g_stamped[0]) hipEventRecord(c->v2g_ev[1], st);
     }
     if (!n) { /* no record: the status words' reset above is all the chain leaves */ }
     else if (general) hipExtLaunchKernelGGL(pv_net_kernel, dim3(grid), dim3(PV_NET_THREADS), 0, st, e0, e1, 0, dp);
@@ -2638,21 +2814,25 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
         if (!combined)
             hipLaunchKernelGGL(c->reg_log2 <= 10 ? pv_topn_combine : pv_topn_combine_r12, dim3(P.cb_grid), dim3(cb_threads), 0, st,
                                (const PvParams *)c->d_params);
-        if (c->geo_counting()) {
-            // top_geo: one walk per combined IP entry (pv_geo_count reads the combine lists; the merge does not change them)
+        if (c->geo_counting() || c->geo2_counting()) {
+            // top_geo: one walk per combined IP entry (pv_geo_count reads the combine lists; the merge does not change them);
+            // v1's entries count into d_cnt, Net v2's per direction into d_cnt2, each only while its handler counts
             PvGeoArgs G{};
             for (int k = 0; k < 2; k++) {
                 const pv_ctx::GeoAttach &g = c->geo[k];
                 if (!g.on) continue;
                 G.tree[k] = g.d_tree;
-                G.cnt[k] = g.d_cnt;
+                G.cnt[k] = c->geo_counting() ? g.d_cnt : nullptr;
+                G.cnt2[k] = c->geo2_counting() ? g.d_cnt2 : nullptr;
                 G.node_count[k] = g.node_count;
                 G.start4[k] = g.start4;
                 G.ip_version[k] = g.ip_version;
                 G.entries[k] = (uint32_t)g.dict.size();
             }
+            if (v2g_timed) { hipEventRecord(c->v2g_ev[2], st); v2g_stamped[1] = true; }
             hipLaunchKernelGGL(pv_geo_count, dim3(std::min<uint32_t>(P.cb_grid, (uint32_t)c->cus * 8)), dim3(256), 0, st,
                                (const PvParams *)c->d_params, G);
+            if (v2g_timed) hipEventRecord(c->v2g_ev[3], st);
         }
         hipLaunchKernelGGL(pv_topn_merge, dim3(2u << c->reg_log2), dim3(pv_topn_merge_threads()), 0, st, (const PvParams *)c->d_params);
     };
@@ -2727,6 +2907,13 @@ int process_span(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_boffs, uint
             for (int k = 0; k < 4; k++) c->dg_ms[k] += part[k];
             c->dg_launches++;
         }
+    }
+    if (v2g_stamped[0] || v2g_stamped[1]) {
+        // (read_status synchronised the stream behind the chain)
+        float ms;
+        for (int k = 0; k < 2; k++)
+            if (v2g_stamped[k] && hipEventElapsedTime(&ms, c->v2g_ev[2 * k], c->v2g_ev[2 * k + 1]) == hipSuccess) c->v2g_ms[k] += ms;
+        c->v2g_launches++;
     }
     if (n) {
         c->dns_heavy = (uint64_t)status[ST_NDNS] * 2 > n;

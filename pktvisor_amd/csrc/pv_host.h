@@ -166,6 +166,7 @@ extern "C" __global__ void pv_geo_walk(const uint32_t *tree, uint32_t node_count
                                        uint32_t addr_words, uint32_t *ids);
 extern "C" __global__ void pv_geo_count(const PvParams *P, PvGeoArgs G);
 extern "C" __global__ void pv_dns_ecs_geo(const uint4 *list, const uint32_t *n_list, uint32_t cap, PvGeoArgs G);
+extern "C" __global__ void pv_dns2_ecs_geo(const uint4 *list, const uint32_t *n_list, uint32_t cap, PvGeoArgs G);
 extern "C" __global__ void pv_dns_geo_verdict(const PvParams *P, PvGeoArgs G, const uint8_t *pass_city, const uint8_t *pass_asn,
                                               uint8_t *out, uint32_t out_cap, uint32_t tcp);
 extern "C" __global__ void pv_geo_verdict(const PvParams *P, PvGeoArgs G, const uint8_t *pass_city, const uint8_t *pass_asn,
@@ -596,8 +597,42 @@ struct pv_ctx {
         // ECS subnets looked up (pv_dns_ecs_geo); cleared with the slot's DNS part. Allocated at the
         // first batch of a context that counts them.
         unsigned long long *d_dcnt = nullptr;
+        // Net v2 geo (pv_set_v2_geo): per Net slot and direction (in, out, unknown), one exact u64
+        // packet count per dictionary id (PV_SLOTS x 3 x dict.size()); allocated by pv_set_geodb only
+        // while the switch is on and Net v2 has top_geo; cleared, folded and reduced with d_cnt
+        unsigned long long *d_cnt2 = nullptr;
+        // DNS v2 geo: per DNS slot and transaction direction, one exact u64 per dictionary id
+        // (PV_SLOTS x 3 x dict.size(); pv_dns2_ecs_geo); allocated at the first batch of a context
+        // that counts them, cleared with the slot's DNS part
+        unsigned long long *d_dcnt2 = nullptr;
         std::vector<pv_geodb::Entry> dict;
     } geo[2];
+    // Net v2 geo (pv_set_v2_geo): the opt-in. Without it a context with Net v2 or DNS v2 refuses a
+    // database, as it always did.
+    bool v2g_on = false;
+    // pv_set_kernel_timing on a v2 geo context: HIP events around the Net v2 pv_geo_verdict launch
+    // ([0], [1]), pv_geo_count ([2], [3]) and pv_dns2_ecs_geo ([4], [5]) of every batch; ms summed
+    // ([0] verdict, [1] Net count, [2] DNS v2 count)
+    hipEvent_t v2g_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double v2g_ms[3] = {0, 0, 0};
+    uint64_t v2g_launches = 0;
+    // the Net v2 handler's own geo filters (pv_set_net2_filters), as nf_* below are v1's: the
+    // reference's two handlers are separate instances with separate filter configs
+    bool nf2_on[2] = {false, false};
+    std::vector<std::string> nf2_prefix[2];
+    uint8_t *d_nf2_pass[2] = {nullptr, nullptr};
+    unsigned long long *d_gfilt2 = nullptr;
+    bool nf2_all() const { return (nf2_on[0] && !geo[0].on) || (nf2_on[1] && !geo[1].on); }
+    bool nf2_verdicts() const { return (nf2_on[0] || nf2_on[1]) && !nf2_all(); }
+    // DNS v2 geo: the transactions dns2_xact lists for pv_dns2_ecs_geo (v2g_list sizes it) and their count
+    uint4 *d_g2list = nullptr;
+    uint32_t *d_g2n = nullptr;
+    uint64_t g2_cap = 0;
+    bool dns2_geo_counting() const { return v2g_on && (geo[0].on || geo[1].on) && (dns2_groups & PV_D2G_TOP_ECS); }
+    bool geo2_counting() const { return v2g_on && (geo[0].on || geo[1].on) && (net2_groups & PV_N2G_TOP_GEO); }
+    // The Net v2 groups as pv_net2_kernel sees them: while top_geo counts, the pass logs the IP
+    // keys the counts come from even with top_ips disabled (the outputs follow net2_groups)
+    uint32_t dev_net2_groups() const { return net2_groups | (geo2_counting() ? (uint32_t)PV_N2G_TOP_IPS : 0u); }
     // DNS v1 geo (pv_set_dns_geo): the opt-in, its two filter families ([0] geoloc_notfound, [1]
     // asn_notfound), and what the first batch builds from them (dg_setup): per family the pass byte
     // per dictionary id (1: the string is "Unknown"), the verdict bytes per record and per TCP
@@ -1031,6 +1066,11 @@ void clear_part(pv_ctx *c, int part, uint32_t s);
 // DNS v1 geo (pv_set_dns_geo): the device state its counts and filters need, built once from the
 // attached databases and the switch (first batch, or the first pv_window_regions); c->mu held
 int dg_setup(pv_ctx *c);
+// DNS v2 geo: room for `need` listed transactions and a zeroed count, ahead of a launch that reaches
+// dns2_xact (X's three fields are set); then pv_dns2_ecs_geo over what the launch listed
+int v2g_setup(pv_ctx *c); // (the counts, at the first batch and wherever dg_setup runs)
+int v2g_list(pv_ctx *c, uint64_t need, PvXactParams &X, hipStream_t st);
+void v2g_count(pv_ctx *c, hipStream_t st);
 void win_shift(pv_ctx *c, Window &w, int64_t T, int64_t Tns = 0);
 uint32_t host_metric(const pv_ctx *c, uint64_t key);
 const std::vector<uint64_t> &hist_points();

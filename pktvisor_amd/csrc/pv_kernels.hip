@@ -899,6 +899,14 @@ __device__ __forceinline__ void dns_process(PV_CREF(PvParams) P, Cache *cache, u
         if (qr) atomicAdd(nresp, 1u);
         PvXEvent ev;
         ev.key = ((uint64_t)dm.fkey << 16) | txid;
+        // A reassembled TCP message the DNS v2 filters reject is handed to process_filtered with its
+        // l3 type where the flow key belongs (tcp_message_ready_cb, dns/v2/DnsStreamHandler.cpp:412),
+        // so its transaction lives under (l3, txid) and the flow's unfiltered messages never meet it
+        // (the reference's ecs.pcap geo KATs pin it: two TCP responses are orphans). Restated for
+        // runs with the v2 geo filters (pv_set_v2_geo) only: other v2 filter runs keep the flow key,
+        // as they always did.
+        if (TCP && filtered && P.dns2_groups && (P.f_flags & (PVDF_GEO_VERDICT | PVDF_FILTER_ALL)))
+            ev.key = ((uint64_t)((dm.flags & 4) ? 6u : 4u) << 16) | txid;
         ev.idx = TCP ? (i | PV_TCP_IDX) : i;
         ev.len = dlen;
         ev.sec = dm.sec;
@@ -955,6 +963,11 @@ __device__ __forceinline__ void dns_process(PV_CREF(PvParams) P, Cache *cache, u
             if constexpr (SFX) {
                 if (!filt && (P.f_flags & PVDF_ONLY_QSUFFIX)) filt = P.sfx_of[i] == 0xffu;
             }
+            // geoloc_notfound / asn_notfound on attached databases (:551-574, the query branch only: a
+            // response never meets them; every filter ends in will_filter, so the position decides
+            // nothing): a family without its database filters every query, else the verdict
+            // pv_dns_geo_verdict wrote for this record (TCP pass: this message)
+            if (!filt) filt = (P.f_flags & PVDF_FILTER_ALL) || ((P.f_flags & PVDF_GEO_VERDICT) && P.dgv[i]);
         }
         if (filt) {
             // process_filtered: an event counted deep when the manager's stale flag is (the
@@ -3006,6 +3019,14 @@ extern "C" __global__ void __launch_bounds__(256) pv_net2_kernel(const PvParams 
         const bool deep = !P.ndeep_net || !((P.ndeep_net[i >> 5] >> (i & 31)) & 1);
         atomicAdd(&ctr[N2_EVENTS], 1u);
         if (deep) atomicAdd(&ctr[N2_SAMPLES], 1u);
+        // the handler's geo filters (NetStreamHandler::_filtering, net/v2/NetStreamHandler.cpp:223-283;
+        // the verdict is pv_geo_verdict's): a filtered packet is the manager's event
+        // (NetworkMetricsManager::process_filtered :748-753, new_event) and the bucket's `filtered`
+        // (NetworkMetricsBucket::process_filtered :486-492), nothing else
+        if (P.net2_filter_all || (P.gfilt2 && ((P.gfilt2[i >> 6] >> (i & 63)) & 1))) {
+            if (g & PV_N2G_COUNTERS) atomicAdd(&ctr[N2_FILTERED], 1u);
+            continue;
+        }
         Parsed o;
         parse_record(R, C, P, P.offs[i], o);
         const uint32_t d = o.dir;
@@ -5161,6 +5182,12 @@ __device__ void dns2_xact(PV_CREF(PvXactParams) X, XState &T, const PvXEvent &e,
         if (g & PV_D2G_COUNTERS) lds_inc(&c[D2_ECS]);
         const NameSrc es{nullptr, nullptr, qaddr, qfam};
         global_add(P, slot, PV_V2_DKEY(TM_ECS, xd, fmix64(qaddr ^ ((uint64_t)qfam << 62) ^ 0xec5ull)), 1, idx, &es);
+        // DNS v2 geo (pv_set_v2_geo; top_geo_loc_ecs_xacts / top_asn_ecs_xacts, :1077-1088): no walk and no
+        // count here, the subnet is listed for pv_dns2_ecs_geo (one rank per counted transaction)
+        if (X.geo2_list) {
+            const uint32_t q = atomicAdd(X.n_geo2, 1u);
+            if (q < X.geo2_cap) reinterpret_cast<PV_G uint4 *>(X.geo2_list)[q] = make_uint4((uint32_t)qaddr, (uint32_t)(qaddr >> 32), qfam | (slot << 8) | (xd << 16), 0u);
+        }
     }
     if (!d.has_query) return;
     NameStats st;
@@ -5820,39 +5847,78 @@ extern "C" hipError_t pv_exclusive_scan_u32(void *tmp, size_t *tmp_bytes, const 
     return rocprim::exclusive_scan(tmp, *tmp_bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s);
 }
 
+// The adds of the geo counting kernels, aggregated across the wave. Most addresses of real traffic
+// share a few ids ("Unknown", the big networks), and one atomic per entry on the same word
+// serialises (8.5 ms a C2 batch, measured). So the wave's lanes of one word add their weights
+// first: up to four such groups a call, led by the lowest lane left; what remains goes one atomic
+// a lane. p: the lane's count word, null for a lane with nothing to add. Every lane of the wave
+// calls it (it votes across the wave). UNIT: every weight is one, so a group's sum is its
+// population count and no reduction runs (the DNS counts).
+template <bool UNIT = false>
+__device__ __forceinline__ void geo_wave_add(unsigned long long *p, unsigned long long w)
+{
+    const int lane = (int)(threadIdx.x & 63);
+    const uint64_t word = (uint64_t)p;
+    uint64_t todo = __ballot(p != nullptr);
+    for (int r = 0; r < 4 && todo; r++) {
+        const int lead = __ffsll((unsigned long long)todo) - 1;
+        const uint64_t lw = __shfl(word, lead, 64);
+        const bool mine = p && word == lw;
+        const uint64_t m = __ballot(mine);
+        unsigned long long sum = UNIT ? (unsigned long long)__popcll(m) : (mine ? w : 0ull);
+        if (!UNIT && (m & (m - 1))) // more than one lane
+            for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        if (lane == lead) atomicAdd(p, sum);
+        todo &= ~m;
+    }
+    if (p && ((todo >> lane) & 1)) atomicAdd(p, w);
+}
+
 // GeoIP / ASN counting (NetworkMetricsBucket::_process_geo_metrics, net/v1/NetStreamHandler.cpp:
-// 376-385,433-442: the address top_ipv4 / top_ipv6 count, looked up in each enabled database).
+// 376-385,433-442: the address top_ipv4 / top_ipv6 count, looked up in each enabled database; the
+// v2 handler's per direction, net/v2/NetStreamHandler.cpp:494-531,697-746: in the source, out the
+// destination, unknown both, which are the PV_V2_IP4 / PV_V2_IP6 keys pv_net2_kernel logs).
 // Runs behind pv_topn_combine over its lists: one entry per distinct address (and direction) of
 // a combine workgroup's records, with the number of packets as its weight, so a heavy hitter
 // costs one tree walk per list instead of one per packet. An IPv4 entry carries the address in
 // its key; an IPv6 key is a hash, so the address is read from the entry's record (the smallest
-// record index among its packets), as the IPv6 name writer reads it. One lane an entry; the
-// walk is pv_geo_step32's (bounded by the address bits, never past node_count); the weight goes
-// to the slot's dense count of the dictionary id.
+// record index among its packets), as the IPv6 name writer reads it (ip6_name_addr: of a v2
+// entry of unknown direction, the one of the record's two addresses whose hash is the key). One
+// lane an entry; the walk is pv_geo_step32's (bounded by the address bits, never past
+// node_count); the weight goes to the slot's dense count of the dictionary id: a v1 entry's to
+// G.cnt [slot][id], a v2 entry's to G.cnt2 [slot][direction][id]. Either array may be null (that
+// handler's top_geo is off): its entries are skipped.
 extern "C" __global__ void __launch_bounds__(256) pv_geo_count(const PvParams *__restrict__ Pp, PvGeoArgs G)
 {
     PV_CREF(PvParams) P = *(const PV_C PvParams *)Pp;
     const uint64_t keymask = (1ull << 60) - 1;
-    const uint32_t lane = threadIdx.x & 63;
+    const bool want1 = G.cnt[0] || G.cnt[1], want2 = G.cnt2[0] || G.cnt2[1];
     for (uint32_t blk = blockIdx.x; blk < P.cb_grid; blk += gridDim.x) {
         const PV_G ulonglong2 *list = reinterpret_cast<const PV_G ulonglong2 *>(P.cb) + (uint64_t)blk * P.cb_fan * P.mq_cap;
         const uint32_t cnt = min(P.cb_cnt[blk], P.cb_fan * P.mq_cap);
         // (whole waves stay in the loop: the counting below votes across the wave)
         for (uint32_t j0 = 0; j0 < cnt; j0 += blockDim.x) {
             const uint32_t j = j0 + threadIdx.x;
-            uint32_t words = 0, a[4] = {0, 0, 0, 0}, w = 0, slot = 0;
+            uint32_t words = 0, a[4] = {0, 0, 0, 0}, w = 0, slot = 0, dir = 0;
+            bool v2 = false;
             if (j < cnt) {
                 const ulonglong2 e = list[j];
                 const uint64_t key = e.x & keymask;
                 const uint32_t metric = PV_KEY_METRIC(key);
                 slot = (uint32_t)(e.x >> 60);
-                if (metric == TM_IPV4 && !PV_IS_V2_IP4(key)) {
-                    a[0] = __builtin_bswap32((uint32_t)key); // the key holds the address as the record's bytes load
-                    words = 1;
-                    w = (uint32_t)e.y & PV_W_CNT;
-                } else if (metric == TM_IPV6 && !PV_IS_V2_IP6(key)) {
+                if (metric == TM_IPV4) {
+                    v2 = PV_IS_V2_IP4(key);
+                    if (v2 ? want2 : want1) {
+                        a[0] = __builtin_bswap32((uint32_t)key); // the key holds the address as the record's bytes load
+                        words = 1;
+                        // (a v1 entry is a dense one: flags above its weight bits)
+                        w = v2 ? (uint32_t)e.y : (uint32_t)e.y & PV_W_CNT;
+                        dir = min((uint32_t)(key >> 34) & 3, 2u);
+                    }
+                } else if (metric == TM_IPV6) {
+                    v2 = PV_IS_V2_IP6(key);
                     const uint32_t rep = (uint32_t)(e.y >> 32);
-                    if (rep < P.n) {
+                    if ((v2 ? want2 : want1) && rep < P.n) {
                         Parsed o;
                         const GAcc R{P.recs};
                         parse_record(R, P, P.offs[rep], o);
@@ -5861,6 +5927,7 @@ extern "C" __global__ void __launch_bounds__(256) pv_geo_count(const PvParams *_
                             for (int k = 0; k < 4; k++) a[k] = __builtin_bswap32(R.u32(at + 4 * k));
                             words = 4;
                             w = (uint32_t)e.y;
+                            dir = min((uint32_t)(key >> 53) & 3, 2u);
                         }
                     }
                 }
@@ -5874,24 +5941,9 @@ extern "C" __global__ void __launch_bounds__(256) pv_geo_count(const PvParams *_
                     id = pv_geo_id(t);
                 }
                 if (id >= G.entries[k]) id = 0; // (a compiled tree holds no such id)
-                // Most addresses of real traffic share a few ids ("Unknown", the big networks), and
-                // one atomic per entry on the same word serialises (8.5 ms a C2 batch, measured).
-                // The wave's lanes of one (slot, id) add their weights first: up to four such groups
-                // a step, led by the lowest lane left; what remains goes one atomic a lane.
-                const uint64_t word = words ? (uint64_t)slot * G.entries[k] + id : ~0ull;
-                uint64_t todo = __ballot(words != 0);
-                for (int r = 0; r < 4 && todo; r++) {
-                    const int lead = __ffsll((unsigned long long)todo) - 1;
-                    const uint64_t lw = __shfl(word, lead, 64);
-                    const bool mine = words && word == lw;
-                    const uint64_t m = __ballot(mine);
-                    unsigned long long sum = mine ? w : 0ull;
-                    if (m & (m - 1)) // more than one lane
-                        for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o, 64);
-                    if ((int)lane == lead) atomicAdd(&G.cnt[k][lw], sum);
-                    todo &= ~m;
-                }
-                if (words && ((todo >> lane) & 1)) atomicAdd(&G.cnt[k][word], (unsigned long long)w);
+                unsigned long long *base = v2 ? G.cnt2[k] : G.cnt[k];
+                const uint64_t row = v2 ? (uint64_t)slot * 3 + dir : (uint64_t)slot;
+                geo_wave_add(words && base ? base + row * G.entries[k] + id : nullptr, w);
             }
         }
     }
@@ -5965,13 +6017,12 @@ __device__ __forceinline__ uint32_t dns_ecs_geo_id(const PvGeoArgs &G, int k, ui
 // dns/v1/DnsStreamHandler.cpp:1026-1048): one lane per query the DNS pass listed for top_ecs
 // ({addr lo, addr hi, family | slot << 8, 0}; the UDP pass's list at pv_dns_ecs's ranks, or the TCP
 // pass's own), one walk per attached database, one to the DNS slot's dense count of the id (G.cnt
-// here: the DNS arrays). The adds are aggregated across the wave as pv_geo_count's are, for the
-// same reason: most subnets of real traffic share a few ids.
+// here: the DNS arrays). The adds are aggregated across the wave as pv_geo_count's are
+// (geo_wave_add): most subnets of real traffic share a few ids.
 extern "C" __global__ void __launch_bounds__(256)
 pv_dns_ecs_geo(const uint4 *__restrict__ list, const uint32_t *__restrict__ n_list, uint32_t cap, PvGeoArgs G)
 {
     const uint32_t n = min(*n_list, cap);
-    const uint32_t lane = threadIdx.x & 63;
     // (whole waves stay in the loop: the counting below votes across the wave)
     for (uint32_t j0 = blockIdx.x * blockDim.x; j0 < n; j0 += gridDim.x * blockDim.x) {
         const uint32_t j = j0 + threadIdx.x;
@@ -5987,17 +6038,36 @@ pv_dns_ecs_geo(const uint4 *__restrict__ list, const uint32_t *__restrict__ n_li
         for (int k = 0; k < 2; k++) {
             if (!G.tree[k]) continue; // (uniform)
             const uint32_t id = fam ? dns_ecs_geo_id(G, k, fam, addr) : 0u;
-            const uint64_t word = fam ? (uint64_t)slot * G.entries[k] + id : ~0ull;
-            uint64_t todo = __ballot(fam != 0);
-            for (int r = 0; r < 4 && todo; r++) {
-                const int lead = __ffsll((unsigned long long)todo) - 1;
-                const uint64_t lw = __shfl(word, lead, 64);
-                const bool mine = fam && word == lw;
-                const uint64_t m = __ballot(mine);
-                if ((int)lane == lead) atomicAdd(&G.cnt[k][lw], (unsigned long long)__popcll(m));
-                todo &= ~m;
-            }
-            if (fam && ((todo >> lane) & 1)) atomicAdd(&G.cnt[k][word], 1ull);
+            geo_wave_add<true>(fam ? G.cnt[k] + (uint64_t)slot * G.entries[k] + id : nullptr, 1ull);
+        }
+    }
+}
+
+// top_geo_loc_ecs_xacts / top_asn_ecs_xacts of the DNS v2 handler (DnsMetricsBucket::new_dns_transaction,
+// dns/v2/DnsStreamHandler.cpp:1077-1088): one lane per transaction dns2_xact listed ({addr lo, addr
+// hi, family | slot << 8 | transaction direction << 16, 0}; every path that reaches dns2_xact lists:
+// same-batch pairs, carried queries, TCP messages, pv_xact_edge2), the address rule and the walk of
+// pv_dns_ecs_geo, one to the DNS slot's dense count [slot][direction][id] (G.cnt here: those arrays).
+extern "C" __global__ void __launch_bounds__(256)
+pv_dns2_ecs_geo(const uint4 *__restrict__ list, const uint32_t *__restrict__ n_list, uint32_t cap, PvGeoArgs G)
+{
+    const uint32_t n = min(*n_list, cap);
+    // (whole waves stay in the loop: geo_wave_add votes across the wave)
+    for (uint32_t j0 = blockIdx.x * blockDim.x; j0 < n; j0 += gridDim.x * blockDim.x) {
+        const uint32_t j = j0 + threadIdx.x;
+        uint32_t fam = 0, row = 0;
+        uint64_t addr = 0;
+        if (j < n) {
+            const uint4 e = list[j];
+            addr = (uint64_t)e.x | (uint64_t)e.y << 32;
+            fam = e.z & 0xff;
+            row = ((e.z >> 8) & 0xff) % PV_SLOTS * 3 + min((e.z >> 16) & 3, 2u); // (bounded whatever the list holds)
+            if (fam != 1 && fam != 2) fam = 0;
+        }
+        for (int k = 0; k < 2; k++) {
+            if (!G.tree[k]) continue; // (uniform)
+            const uint32_t id = fam ? dns_ecs_geo_id(G, k, fam, addr) : 0u;
+            geo_wave_add<true>(fam ? G.cnt[k] + (uint64_t)row * G.entries[k] + id : nullptr, 1ull);
         }
     }
 }

@@ -517,6 +517,11 @@ struct PvParams {
     PV_G uint32_t *n_ecs_tcp; // status word
     uint32_t ecs_tcp_cap;
     const PV_G uint8_t *dgv;
+    // The Net v2 handler's own geo filters (pv_set_net2_filters): bit i set = record i is a filtered
+    // Net v2 event (pv_geo_verdict's second launch writes it, pv_net2_kernel reads it); null = none.
+    // net2_filter_all: a family is set while its database is not attached, every packet is filtered.
+    const PV_G uint64_t *gfilt2;
+    uint32_t net2_filter_all;
 };
 
 // pv_fill_multi's segment list (kernel argument)
@@ -589,6 +594,11 @@ struct PvXactParams {
     // is below this horizon are appended to the stub list too (a query of an earlier shard still
     // open there is overwritten by them, TransactionManager::start_transaction); 0 = none
     int64_t edge_h;
+    // DNS v2 geo (pv_set_v2_geo; null without it): dns2_xact lists {addr lo, addr hi, family | slot << 8
+    // | xd << 16, 0} of every counted transaction whose query carried a subnet, for pv_dns2_ecs_geo
+    PV_G uint32_t *geo2_list; // (uint4 entries)
+    PV_G uint32_t *n_geo2;
+    uint32_t geo2_cap;
 };
 #define PV_PEND_FLAG 0x80000000u
 // A DNS v2 transaction across a shard edge (pv_edge_carry): a query an earlier shard left open

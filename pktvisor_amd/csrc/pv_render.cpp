@@ -94,7 +94,11 @@ enum { TMH_V2_IP4 = 32, TMH_V2_IP6 = 36, TMH_V2_DNS = 64 }; // DNS v2: 64 + 4 * 
 // merges, external buckets from contexts with other databases); geo_item splits it again.
 enum { TMH_GEO_LOC = 40, TMH_GEO_ASN = 41,
        // the DNS v1 handler's top_geoLoc_ecs / top_asn_ecs (pv_set_dns_geo), carried the same way
-       TMH_GEO_LOC_ECS = 42, TMH_GEO_ASN_ECS = 43 };
+       TMH_GEO_LOC_ECS = 42, TMH_GEO_ASN_ECS = 43,
+       // the Net v2 handler's top_geo_loc_packets / top_asn_packets (pv_set_v2_geo), + direction
+       TMH_V2_GEO_LOC = 44, TMH_V2_GEO_ASN = 47,
+       // the DNS v2 handler's top_geo_loc_ecs_xacts / top_asn_ecs_xacts, + transaction direction
+       TMH_V2_GEO_LOC_ECS = 50, TMH_V2_GEO_ASN_ECS = 53 };
 #define PV_GEO_SEP '\x1f'
 // (split from the right: latitude and longitude are "%f" renderings and hold no separator, so a
 // location string may hold any byte; only lists the caller marks as geo are split at all)
@@ -286,6 +290,23 @@ int load_bucket(pv_ctx *c, const std::vector<uint32_t> &slots, bool merged, int 
                     b.tops[k == 0 ? TMH_GEO_LOC : TMH_GEO_ASN][en.name + PV_GEO_SEP + en.lat + PV_GEO_SEP + en.lon] += cnt[i];
                 }
             }
+        if (part == PART_NET)
+            for (int k = 0; k < 2; k++) {
+                // Net v2 top_geo: the slot's exact counts per direction and dictionary id, by rendered string
+                const pv_ctx::GeoAttach &g = c->geo[k];
+                if (!g.d_cnt2 || !c->geo2_counting()) continue;
+                std::vector<uint64_t> cnt(3 * g.dict.size());
+                if (!hip_ok(e = hipMemcpyAsync(cnt.data(), g.d_cnt2 + (uint64_t)s * cnt.size(), cnt.size() * 8, hipMemcpyDeviceToHost,
+                                               c->stream)) ||
+                    !hip_ok(e = hipStreamSynchronize(c->stream)))
+                    return c->hipfail(e, "read Net v2 geo counts");
+                for (size_t i = 0; i < cnt.size(); i++) {
+                    if (!cnt[i]) continue;
+                    const pv_geodb::Entry &en = g.dict[i % g.dict.size()];
+                    b.tops[(k == 0 ? TMH_V2_GEO_LOC : TMH_V2_GEO_ASN) + (uint32_t)(i / g.dict.size())]
+                          [en.name + PV_GEO_SEP + en.lat + PV_GEO_SEP + en.lon] += cnt[i];
+                }
+            }
         if (part != PART_DNS) continue;
         for (int k = 0; k < 2; k++) {
             // top_geoLoc_ecs / top_asn_ecs: the DNS slot's exact counts per dictionary id, by rendered string
@@ -300,6 +321,22 @@ int load_bucket(pv_ctx *c, const std::vector<uint32_t> &slots, bool merged, int 
                 if (!cnt[i]) continue;
                 const pv_geodb::Entry &en = g.dict[i];
                 b.tops[k == 0 ? TMH_GEO_LOC_ECS : TMH_GEO_ASN_ECS][en.name + PV_GEO_SEP + en.lat + PV_GEO_SEP + en.lon] += cnt[i];
+            }
+        }
+        for (int k = 0; k < 2; k++) {
+            // DNS v2 top_geo_loc_ecs_xacts / top_asn_ecs_xacts: the DNS slot's exact counts per direction and id
+            const pv_ctx::GeoAttach &g = c->geo[k];
+            if (!g.d_dcnt2 || !c->dns2_geo_counting()) continue;
+            std::vector<uint64_t> cnt(3 * g.dict.size());
+            if (!hip_ok(e = hipMemcpyAsync(cnt.data(), g.d_dcnt2 + (uint64_t)s * cnt.size(), cnt.size() * 8, hipMemcpyDeviceToHost,
+                                           c->stream)) ||
+                !hip_ok(e = hipStreamSynchronize(c->stream)))
+                return c->hipfail(e, "read DNS v2 geo counts");
+            for (size_t i = 0; i < cnt.size(); i++) {
+                if (!cnt[i]) continue;
+                const pv_geodb::Entry &en = g.dict[i % g.dict.size()];
+                b.tops[(k == 0 ? TMH_V2_GEO_LOC_ECS : TMH_V2_GEO_ASN_ECS) + (uint32_t)(i / g.dict.size())]
+                      [en.name + PV_GEO_SEP + en.lat + PV_GEO_SEP + en.lon] += cnt[i];
             }
         }
         const uint32_t sg = s | (c->gen[s] << 8);
@@ -530,8 +567,9 @@ void net2_json(pv_ctx *c, Json &j, const HostBucket &b)
             top_json(j, "top_ipv6_packets", tops_of(b, TMH_V2_IP6 + d), topn, pct);
         }
         if (g & PV_N2G_TOP_GEO) {
-            j.key("top_geo_loc_packets").arr(); j.end_arr();
-            j.key("top_asn_packets").arr(); j.end_arr();
+            // (empty without a database and the v2 geo switch: an external bucket carries its own)
+            top_json(j, "top_geo_loc_packets", tops_of(b, TMH_V2_GEO_LOC + d), topn, pct, true);
+            top_json(j, "top_asn_packets", tops_of(b, TMH_V2_GEO_ASN + d), topn, pct, true);
         }
         if (g & PV_N2G_QUANTILES) {
             uint64_t cnt;
@@ -589,9 +627,10 @@ void dns2_json(pv_ctx *c, Json &j, const HostBucket &b)
         if (g & PV_DNS2_TOP_PORTS)
             top_json(j, "top_udp_ports_xacts", dense_tops(&b.sum[PV_OFF_PORT2 + x * PV_PORT_BINS], PV_PORT_BINS, 0), topn, pct);
         if (g & PV_DNS2_TOP_ECS) {
-            // geo / ASN of the subnet need a MaxMind database; none is enabled (HandlerModulePlugin::city/asn)
-            j.key("top_geo_loc_ecs_xacts").arr(); j.end_arr();
-            j.key("top_asn_ecs_xacts").arr(); j.end_arr();
+            // geo / ASN of the subnet need a MaxMind database and the v2 geo switch (pv_set_v2_geo);
+            // without them the maps are empty (an external bucket carries its own)
+            top_json(j, "top_geo_loc_ecs_xacts", tops_of(b, TMH_V2_GEO_LOC_ECS + x), topn, pct, true);
+            top_json(j, "top_asn_ecs_xacts", tops_of(b, TMH_V2_GEO_ASN_ECS + x), topn, pct, true);
             top_json(j, "top_ecs_xacts", tops(TM_ECS), topn, pct);
         }
         if (g & PV_DNS2_TOP_RCODES) {
@@ -1094,7 +1133,7 @@ void dns_metrics(pv_ctx *c, Sink &p, const HostBucket &b)
 // NetworkMetricsBucket::to_prometheus / to_opentelemetry, Net v2
 // (src/handlers/net/v2/NetStreamHandler.cpp:333-383; names NetStreamHandler.h:72-181): the
 // event counts, `filtered_packets`, then per direction the bucket has seen, labelled
-// direction=in|out|unknown (rates are timer-driven and out of scope; geo / ASN TopNs empty)
+// direction=in|out|unknown (rates are timer-driven and out of scope; geo / ASN TopNs: pv_set_v2_geo)
 template <class Sink>
 void net2_metrics(pv_ctx *c, Sink &p, const HostBucket &b)
 {
@@ -1126,6 +1165,11 @@ void net2_metrics(pv_ctx *c, Sink &p, const HostBucket &b)
         if (g & PV_N2G_TOP_IPS) {
             p.topn("net_top_ipv4_packets", "ipv4", "Top IPv4 addresses", tops_of(b, TMH_V2_IP4 + d), topn, pct);
             p.topn("net_top_ipv6_packets", "ipv6", "Top IPv6 addresses", tops_of(b, TMH_V2_IP6 + d), topn, pct);
+        }
+        if (g & PV_N2G_TOP_GEO) {
+            // (net/v2/NetStreamHandler.h:139-140; an empty TopN writes nothing)
+            p.topn("net_top_geo_loc_packets", "geo_loc", "Top GeoIP locations", tops_of(b, TMH_V2_GEO_LOC + d), topn, pct, true);
+            p.topn("net_top_asn_packets", "asn", "Top ASNs by IP", tops_of(b, TMH_V2_GEO_ASN + d), topn, pct, true);
         }
         if (g & PV_N2G_QUANTILES) {
             uint64_t cnt;
@@ -1193,9 +1237,12 @@ void dns2_metrics(pv_ctx *c, Sink &p, const HostBucket &b)
         if (g & PV_DNS2_TOP_PORTS)
             p.topn("dns_top_udp_ports_xacts", "port", "Top UDP source port on the query side of a transaction",
                    dense_tops(&b.sum[PV_OFF_PORT2 + x * PV_PORT_BINS], PV_PORT_BINS, 0), topn, pct);
-        if (g & PV_DNS2_TOP_ECS)
-            // geo / ASN of the subnet: no MaxMind database, those TopNs write nothing
+        if (g & PV_DNS2_TOP_ECS) {
+            // geo / ASN of the subnet (pv_set_v2_geo; dns/v2/DnsStreamHandler.h:255-256); an empty TopN writes nothing
+            p.topn("dns_top_geo_loc_ecs_xacts", "geo_loc", "Top GeoIP ECS locations", tops_of(b, TMH_V2_GEO_LOC_ECS + x), topn, pct, true);
+            p.topn("dns_top_asn_ecs_xacts", "asn", "Top ASNs by ECS", tops_of(b, TMH_V2_GEO_ASN_ECS + x), topn, pct, true);
             p.topn("dns_top_ecs_xacts", "ecs", "Top EDNS Client Subnet (ECS) observed in DNS transaction", tops(TM_ECS), topn, pct);
+        }
         if (g & PV_DNS2_TOP_RCODES) {
             p.topn("dns_top_nxdomain_xacts", "qname", "Top QNAMES with result code NXDOMAIN", tops(TM_NX), topn, pct);
             p.topn("dns_top_refused_xacts", "qname", "Top QNAMES with result code REFUSED", tops(TM_REFUSED), topn, pct);

@@ -960,6 +960,7 @@ int pv_window_regions(pv_ctx *c, pv_region *r, uint32_t max, uint32_t *n)
     std::lock_guard<std::mutex> g(c->mu);
     // (a rank that has seen no batch lists the same regions as the others)
     if (int rc = dg_setup(c)) return rc;
+    if (int rc = v2g_setup(c)) return rc;
     flush_fills(c);
     std::vector<pv_region> v;
     // the parts of each slot the attached handler versions use (the others stay zero)
@@ -975,6 +976,9 @@ int pv_window_regions(pv_ctx *c, pv_region *r, uint32_t max, uint32_t *n)
         // the slot's geo counts (ranks attach identical databases: the dictionary ids are a function of the file)
         for (auto &g : c->geo)
             if (g.d_cnt) v.push_back(pv_region{g.d_cnt + (size_t)s * g.dict.size(), g.dict.size(), PV_REDUCE_SUM, 0});
+        // Net v2 geo (pv_set_v2_geo): the slot's three directions' counts, under the same hash check
+        for (auto &g : c->geo)
+            if (g.d_cnt2) v.push_back(pv_region{g.d_cnt2 + (size_t)s * 3 * g.dict.size(), 3 * g.dict.size(), PV_REDUCE_SUM, 0});
         c->net.clean[s] = false;
     }
     for (uint32_t s : c->dns.slots) {
@@ -989,6 +993,9 @@ int pv_window_regions(pv_ctx *c, pv_region *r, uint32_t max, uint32_t *n)
             for (auto &g : c->geo)
                 if (g.d_dcnt) v.push_back(pv_region{g.d_dcnt + (size_t)s * g.dict.size(), g.dict.size(), PV_REDUCE_SUM, 0});
         }
+        // DNS v2 geo (pv_set_v2_geo): the slot's three transaction directions' counts, as the Net ones above
+        for (auto &g : c->geo)
+            if (g.d_dcnt2) v.push_back(pv_region{g.d_dcnt2 + (size_t)s * 3 * g.dict.size(), 3 * g.dict.size(), PV_REDUCE_SUM, 0});
         c->dns.clean[s] = false;
     }
     *n = (uint32_t)v.size();
@@ -1422,6 +1429,8 @@ int edge_carry2(pv_ctx *c, const uint8_t *in, size_t in_bytes, uint8_t **out, si
         X.trecs = (const uint8_t *)d[2];
         X.toffs = (const uint32_t *)d[3];
         X.tsfx = (const uint8_t *)d[5];
+        // DNS v2 geo: the edge pairs count in top_ecs as any transaction does, one listed entry a pair
+        if (int rc = v2g_list(c, run.size(), X, c->stream)) return rc;
         flush_fills(c);
         *c->h_xparams = X;
         if (!hip_ok(e = hipMemcpyAsync(c->d_xparams, c->h_xparams, sizeof X, hipMemcpyHostToDevice, c->stream)))
@@ -1429,6 +1438,7 @@ int edge_carry2(pv_ctx *c, const uint8_t *in, size_t in_bytes, uint8_t **out, si
         hipLaunchKernelGGL(pv_xact_edge2, dim3((uint32_t)((run.size() + 255) / 256)), dim3(256), 0, c->stream,
                            (const PvXactParams *)c->d_xparams, (const PvEdgePair *)d[6], (uint32_t)run.size(), (uint8_t *)d[4],
                            (uint8_t *)d[5]);
+        if (X.geo2_list) v2g_count(c, c->stream);
         if (!hip_ok(e = hipGetLastError()) || !hip_ok(e = hipStreamSynchronize(c->stream))) return c->hipfail(e, "pv_xact_edge2");
     }
     uint32_t flags = 0;
