@@ -2182,12 +2182,33 @@ __device__ __forceinline__ void net_ranges(PV_CREF(PvParams) P, bool contig, uin
 // has two sections, and one barrier a section (every PV_RING_K tiles of each wave: one turn of the
 // pipeline loop below) both publishes the section just filled and frees the other. Every wave runs
 // the range's section count of turns, a wave past its last tile filling its slots with zeros.
+#define PV_RING_CTRS 12 // knet_flush's words of a pass without filters
 struct FuseRing {
     struct Sec {
         uint32_t ip[PV_RING_SLOTS][PV_WT]; // a record's logged address: the IP log's word
         uint64_t dm[PV_RING_SLOTS];        // a tile's direction mask: its ipdir word
     } sec[2];
+    // the hand-over's words, so that the combine tail waits for no global store of the Net phase:
+    uint32_t ctr[PV_RING_CTRS]; // the Net waves' counters, summed: one global add a word and workgroup
+    uint32_t bad;               // S.nd | S.ns of every range so far: a DNS message or a deferred record
+    uint32_t pad;
 };
+// -DPV_RING_SYNC_TAIL, a probe build: the hand-over as it was (the Net waves wait for their stores
+// and atomics, every barrier after it is a __syncthreads()). -DPV_RING_WAVE_FLUSH, a probe build:
+// knet_flush a Net wave as in the logged kernel. -DPV_RING_NOFLUSH, a probe build: no counter and
+// no histogram flush at all (wrong counters; timing only). profiles/r12/ring_handover
+#ifdef PV_RING_SYNC_TAIL
+#define PV_RING_LDS_TAIL false
+#else
+#define PV_RING_LDS_TAIL true
+#endif
+// a workgroup barrier of the combine tail: LDS-only on the ring path
+template <bool LDS>
+__device__ __forceinline__ void tail_barrier()
+{
+    if constexpr (LDS) lds_barrier();
+    else __syncthreads();
+}
 template <uint32_t NW, bool TC = false, bool FUSE = false, bool RING = false>
 __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp, FuseRing *ring = nullptr)
 {
@@ -2199,6 +2220,10 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp, Fu
     for (uint32_t b = threadIdx.x; b < PV_HBINS; b += (FUSE ? 64u * NW : blockDim.x)) S.hist[b] = 0;
     if (threadIdx.x == 0) { S.nd = 0; S.nx = 0; S.ns = 0; }
     if (threadIdx.x < PV_MAX_SHIFTS) S.dord[threadIdx.x] = P.dpos[threadIdx.x];
+    if constexpr (RING) {
+        if (threadIdx.x < PV_RING_CTRS) ring->ctr[threadIdx.x] = 0;
+        if (threadIdx.x == 0) ring->bad = 0;
+    }
     __syncthreads();
     const PV_G uint8_t *const recs = P.recs;
     const bool compact = P.ip_compact;
@@ -2406,8 +2431,16 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp, Fu
     // barriers: the range's IP-log and DNS-list stores are other kernels' to read, and waiting
     // for them here would stall every wave on their completion; FUSE: the waves beside the Net
     // phase read the range's IP log after these barriers, so there the wait is taken)
-    // (RING: no log, nothing to wait for)
+    // (RING: no log. What is in flight here is the last turn's prefetches, clamped copies of a
+    // tile just read, and the range before's four count stores. The wait is for the prefetches:
+    // a load still pending when the combine tail reuses its registers would make the compiler put
+    // a vmcnt(0) there, behind the count stores and counter atomics that follow this line, and
+    // the tail is to wait for none of those. -DPV_RING_NO_RANGE_WAIT, a probe build: without it)
+#ifdef PV_RING_NO_RANGE_WAIT
     if constexpr (FUSE && !RING) __builtin_amdgcn_s_waitcnt(PV_WAIT_VMCNT0);
+#else
+    if constexpr (FUSE && (!RING || PV_RING_LDS_TAIL)) __builtin_amdgcn_s_waitcnt(PV_WAIT_VMCNT0);
+#endif
     lds_barrier();
     if (threadIdx.x == 0) {
         P.mq_cnt[lb] = 0;
@@ -2416,6 +2449,8 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp, Fu
         P.slow_cnt[lb] = S.ns;
         if (S.nd) atomicAdd(P.n_dns, S.nd);
         if (S.ns) atomicAdd(P.n_slow, S.ns);
+        // (RING: the combine tail's word of every range of the group, published by the barrier below)
+        if constexpr (RING) ring->bad |= S.nd | S.ns;
         S.nd = 0;
         S.nx = 0;
         S.ns = 0;
@@ -2432,8 +2467,37 @@ __device__ __forceinline__ void net_fast_reg(const PvParams *__restrict__ Pp, Fu
     }
     NetK K;
     K.sum = P.sum; K.net_groups = groups; K.net_filter_all = 0; K.gfilt = nullptr;
-    if (any) knet_flush(K, slot, c);
+#if defined(PV_RING_NOFLUSH)
+    constexpr bool FLUSH = !RING, WGFLUSH = false;
+#elif defined(PV_RING_WAVE_FLUSH)
+    constexpr bool FLUSH = true, WGFLUSH = false;
+#else
+    constexpr bool FLUSH = true, WGFLUSH = RING;
+#endif
+    if constexpr (WGFLUSH) {
+        // knet_flush's words (NC_EVENTS .. NC_TOTAL; no filter, so no NC_FILTERED) summed over the
+        // Net waves in LDS, then one agent-scope add a word from the workgroup, not one a wave:
+        // every workgroup's adds land on the same one or two lines within the same microseconds
+        static_assert(NC_TOTAL + 1 == PV_RING_CTRS && NC_FILTERED == PV_RING_CTRS, "the counter words, contiguous");
+        auto put = [&](uint32_t w, uint32_t v) {
+            const uint32_t t = wave_sum(v);
+            if (lane == 0 && t) atomicAdd(&ring->ctr[w], t);
+        };
+        put(NC_EVENTS, c.nev); put(NC_SAMPLES, c.nev); put(NC_TOTAL, c.nev - c.nfilt); put(NC_IN, c.nin);
+        put(NC_OUT, c.nout); put(NC_UNK, c.nunk); put(NC_V4, c.n4); put(NC_V6, c.n6);
+        put(NC_UDP, c.nudp); put(NC_TCP, c.ntcp); put(NC_SYN, c.nsyn); put(NC_OTHER, c.noth);
+    } else if constexpr (FLUSH) {
+        if (any) knet_flush(K, slot, c);
+    }
     lds_barrier();
+    if constexpr (WGFLUSH) {
+        if (threadIdx.x < PV_RING_CTRS) {
+            const uint32_t t = ring->ctr[threadIdx.x];
+            if (t && (threadIdx.x == NC_EVENTS || threadIdx.x == NC_SAMPLES || (groups & PV_NET_COUNTERS_BIT)))
+                ksum_add(K, slot, PV_OFF_NET + threadIdx.x, t);
+        }
+    }
+    if constexpr (FLUSH)
     for (uint32_t b = threadIdx.x; b < PV_HBINS; b += (FUSE ? 64u * NW : blockDim.x))
         if (S.hist[b]) ksum_add(K, slot, PV_OFF_PAYLOAD + b, S.hist[b]);
     TST_WALL(P, 1)
@@ -3405,6 +3469,8 @@ __device__ __forceinline__ void comb_cadd_pre(PV_CREF(PvParams) P, St &S, PV_G u
 }
 
 // exclusive prefix of v over the workgroup (all threads call it); *total = the sum
+// (LDS: its two barriers as lds_barrier(), for pv_net_combine_ring's tail)
+template <bool LDS = false>
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, uint32_t &total)
 {
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
@@ -3415,14 +3481,14 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, 
         if (lane >= (uint32_t)o) incl += t;
     }
     if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
+    tail_barrier<LDS>();
     uint32_t base = 0, tot = 0;
     for (uint32_t k = 0; k < nw; k++) {
         const uint32_t s = wsum[k];
         if (k < wv) base += s;
         tot += s;
     }
-    __syncthreads();
+    tail_barrier<LDS>();
     total = tot;
     return base + incl - v;
 }
@@ -3534,7 +3600,9 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
         if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < NETW) {
             net_fast_reg<NETW, true, true, RING>(Pp, ring);
             // hand-over, this side: every store of the Net phase acknowledged by the L2
-            __builtin_amdgcn_s_waitcnt(PV_WAIT_VMCNT0);
+            // (RING: the tail reads none of them back. Its one word of the Net phase, `bad`, is
+            // in LDS, so the count stores and the counter atomics complete beside the tail)
+            if constexpr (!(RING && PV_RING_LDS_TAIL)) __builtin_amdgcn_s_waitcnt(PV_WAIT_VMCNT0);
         } else if constexpr (RING) {
             // the Net phase's barriers, as below, and one a section in between: after it the
             // section's twelve slots are complete and the other section is the Net waves' to fill,
@@ -3564,6 +3632,10 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
                 lds_barrier();
                 lds_barrier();
             }
+            // this wave's spill stores, which the out pass reads back: acknowledged before the
+            // barriers that lie between here and that read (no later barrier of the ring path
+            // waits for a global store; the wave would only park at the Net phase's last barrier)
+            __builtin_amdgcn_s_waitcnt(PV_WAIT_VMCNT0);
             lds_barrier();
         } else {
             // the Net phase's init barrier first (the Net waves start streaming at once), then
@@ -3582,9 +3654,10 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
             }
             lds_barrier();
         }
-        __syncthreads();
+        tail_barrier<RING && PV_RING_LDS_TAIL>();
         TST_WALL(P, 2)
     }
+    constexpr bool LT = RING && PV_RING_LDS_TAIL; // the tail's barriers: LDS-only
     // the short chain (no DNS pass, no pv_net_slow_list ahead of this kernel): a batch the Net pass
     // found a DNS message or a deferred record in is left as it is for the regular chain, which the
     // host runs next: no list, no run word, no cb_hm word, no tp_hands bit (pv_topn_merge then
@@ -3602,7 +3675,10 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
         // own ranges' and leaves them untouched when either is set (the same value in every
         // thread). Other workgroups may have combined theirs by then: pv_topn_merge returns at its
         // first line on such a batch, and the regular chain's combine rewrites what they wrote.
+        // (RING: the same two counts of every range, ORed in LDS as the Net phase stored them)
         uint32_t bad = 0;
+        if constexpr (LT) bad = fuse_ring<RING>()->bad;
+        else
         for (uint32_t gr = g0; gr < g1; gr++) bad |= ld_own<true>(P.dq_cnt + gr) | ld_own<true>(P.slow_cnt + gr);
         if (bad) return;
     }
@@ -3625,6 +3701,8 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
             wg_records(P, g0, a0, z0);
             wg_records(P, g1 - 1, a1, z1);
             other = z1 - a0 > 65535 ? 1u : 0u;
+            // (RING: the host's decision, see `compact` below: the words are not read)
+            if constexpr (!LT)
             for (uint32_t gr = g0; gr < g1; gr++) other |= ld_own<FUSE>(P.mq_cnt + gr) | ld_own<FUSE>(P.ipx_cnt + gr);
             cbase = (uint32_t)a0;
         }
@@ -3727,12 +3805,14 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
     }
     }
     if (threadIdx.x == 0) S.hm = 0;
-    __syncthreads();
+    tail_barrier<LT>();
     TST(1)
     // the table's entries per region (the spilled ones were counted as they spilled). Counting
     // an entry where its CAS claims it instead was measured and is slower: the claiming lanes are
     // a fifth of a wave there (C2 insert phase 37.5K -> 56.3K cycles for this pass's 6.4K,
-    // profiles/r7/topn_seen)
+    // profiles/r7/topn_seen; in pv_net_combine_ring, where the insert runs beside the Net phase,
+    // it shortens this pass from 8.3K to 5.2K cycles and the Net phase ends 2-3 us later: no gain
+    // in the step, profiles/r12/ring_handover)
     // (compact mode: a thread's CK slots' run keys stay in registers, two a word, for the out pass)
     uint32_t rk[CK / 2] = {};
     if (compact) {
@@ -3748,7 +3828,7 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
     } else
     for (uint32_t j = threadIdx.x; j < CN; j += blockDim.x)
         if (S.key[j]) comb_count(P, S, comb_entry(S.key[j], S.cnt[j], S.rep[j]).x);
-    __syncthreads();
+    tail_barrier<LT>();
     TST(2)
     // region run starts: each thread scans a contiguous share of the regions
     const uint32_t per = (nreg + blockDim.x - 1) / blockDim.x;
@@ -3762,7 +3842,7 @@ __device__ __forceinline__ void topn_combine(PV_CREF(PvParams) P, const PvParams
         if ((threadIdx.x & 63) == 0 && (b0 | b1)) atomicOr(&S.hm, (b0 ? 1u : 0u) | (b1 ? 2u : 0u));
     }
     uint32_t total;
-    uint32_t run = block_excl_scan(s, S.wsum, total); // (its barriers publish S.hm)
+    uint32_t run = block_excl_scan<LT>(s, S.wsum, total); // (its barriers publish S.hm)
     const uint32_t hm = S.hm;
     // handlers with entries in this batch (pv_topn_merge's workgroups of the other exit early)
     if (threadIdx.x < 2 && ((hm >> threadIdx.x) & 1)) atomicOr(P.tp_hands, 1u << threadIdx.x);
