@@ -2570,6 +2570,28 @@ void pvo_dns_parse(const uint8_t *msg, uint32_t len, int *ok, int *has_query, ui
     *ok = r.ok; *has_query = r.has_query; *qtype = r.qtype;
 }
 
+// only_dnssec_response's walk, the first additional record's offset (-1: none) and the ECS
+// subnet text (its length returned, 0: none) of one message of at least 12 bytes
+int pvo_dns_dnssec(const uint8_t *msg, uint32_t len)
+{
+    pvo::DnsMsg m{msg, len};
+    return pvo::dnssec_answer(m) ? 1 : 0;
+}
+
+long pvo_first_additional(const uint8_t *msg, uint32_t len)
+{
+    pvo::DnsMsg m{msg, len};
+    return pvo::first_additional(m);
+}
+
+uint32_t pvo_dns_ecs(const uint8_t *msg, uint32_t len, char *out)
+{
+    pvo::DnsMsg m{msg, len};
+    const std::string s = pvo::ecs_subnet(m);
+    memcpy(out, s.data(), s.size());
+    return (uint32_t)s.size();
+}
+
 void pvo_aggregate_domain(const char *name, size_t n, size_t suffix, size_t *q2_start, long *q3_start)
 {
     std::string d(name, n), q2, q3;

@@ -2932,9 +2932,11 @@ __device__ __forceinline__ void dns_pass(const PvParams *__restrict__ Pp)
             }
             const uint64_t wbase = (uint64_t)dm.moff & ~15ull;
             if (PV_DNS_LACC) {
-                // a message the window holds whole (every byte the decoder reads lies in
-                // [moff, moff + max(mlen, mcap))) decodes from LDS alone; the rest wait for the
-                // range's long pass, where no prefetch is in flight
+                // a message the window holds whole decodes from LDS alone: every byte the decode's
+                // result depends on lies in [moff, moff + max(mlen, mcap)). (name_stats_fast loads up
+                // to 18 bytes more, masked off: words of the next wave's stage, see pv_parse.h; the
+                // device decode fuzz, tests/test_gpu_dns_decode.py, holds both.) The rest wait for
+                // the range's long pass, where no prefetch is in flight
                 const bool fits = (uint64_t)dm.moff + max((uint32_t)dm.mlen, (uint32_t)dm.mcap) - wbase <= (uint64_t)(PV_WIN - 4);
                 if (active && fits) {
                     const LAcc R{L, wbase, (uint32_t)PV_WT, lane};

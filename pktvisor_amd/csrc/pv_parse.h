@@ -613,6 +613,13 @@ struct BufEmit {
 // substitution from the label walk, murmur over 16-byte blocks, prefix hashes at the
 // last four dots taken from the running Horner values); it returns false, st untouched,
 // for every other name.
+// It loads whole words: the word behind each of the name's 16-byte blocks is fetched before
+// the block's length is known, so it reads at most 18 bytes past the message (a name of
+// 16 k + 1 bytes that ends the message, its text starting on a word boundary; 17 measured with
+// the message itself on one, tests/test_decoder_fuzz.py). Those bytes are masked off (vm) and
+// the result does not depend on them; they are the one read of the DNS decode outside
+// [m, m + len). Past the end of an LDS window (LAcc) they are words of the next wave's stage
+// or of what follows the stages in LDS; in HBM, at worst the record blob's padding (PV_RECS_PAD).
 PV_FN uint32_t lower4(uint32_t w)
 {
     const uint32_t t = w & 0x7f7f7f7fu;

@@ -84,6 +84,104 @@ int h_name_fast_check(const uint8_t *msg, uint32_t len)
 }
 }
 
+// plain-memory accessor that records how far its reads went: the end of the highest byte read,
+// with a word read counted as its four bytes
+struct TrAcc {
+    const uint8_t *R;
+    uint64_t *hi;
+    void note(uint64_t end) const { if (end > *hi) *hi = end; }
+    uint32_t u32(uint64_t off) const { note(off + 4); uint32_t v; memcpy(&v, R + off, 4); return v; }
+    uint32_t u32a(uint64_t off) const { return u32(off); }
+    uint32_t u8(uint64_t off) const { note(off + 1); return R[off]; }
+};
+
+// The 12 header bytes the way the kernels' dns_header takes them: bytes past the message read as 0
+static uint32_t hdr16(const uint8_t *msg, uint32_t len, uint32_t off)
+{
+    return ((off < len ? msg[off] : 0u) << 8) | (off + 1 < len ? msg[off + 1] : 0u);
+}
+
+// Every DNS entry point of pv_parse.h on one message, through one accessor. v[PV_DNS_ALL_VALS]:
+// name_len_l1; dns_parse ok, has_query, qtype, name_len_enc; NameStats n, murmur halves, the
+// aggregateDomain starts; the fast path's verdict (h_name_fast_check's); dns_dnssec;
+// dns_first_additional; dns_ecs family and address. name: name_emit's bytes.
+#define PV_DNS_ALL_VALS 15
+template <class A>
+static void dns_all(const A &R, const uint8_t *msg, uint32_t len, uint64_t *v, char *name, uint32_t *name_n)
+{
+    struct Coll {
+        char *o;
+        uint32_t n;
+        void put(uint32_t c) { o[n++] = (char)c; }
+    } col{name, 0};
+    const uint32_t qd = hdr16(msg, len, 4), an = hdr16(msg, len, 6), ns = hdr16(msg, len, 8), ar = hdr16(msg, len, 10);
+    const uint32_t nl = name_len_l1(R, 0, len, 12);
+    if (nl > 0) name_emit(R, 0, len, 12, col);
+    *name_n = col.n;
+    v[0] = nl;
+    DnsInfo d;
+    dns_parse(R, 0, len, qd, an, ns, ar, d);
+    v[1] = d.ok; v[2] = d.has_query; v[3] = d.qtype; v[4] = d.name_len_enc;
+    NameStats st, fs;
+    st.init();
+    fs.init();
+    if (nl > 0) name_emit(R, 0, len, 12, st);
+    v[5] = st.n;
+    Murmur mm = st.mm;
+    mm.finish(v[6], v[7]);
+    int q2 = 0, q3 = -1;
+    uint64_t a, b;
+    if (st.n) agg_domain(st, q2, q3, a, b);
+    v[8] = (uint64_t)(int64_t)q2; v[9] = (uint64_t)(int64_t)q3;
+    v[10] = (uint64_t)(int64_t)-1;
+    if (nl > 0 && name_stats_fast(R, 0, len, 12, fs)) {
+        uint64_t f1, f2;
+        fs.mm.finish(f1, f2);
+        v[10] = f1 == v[6] && f2 == v[7] && fs.ph == st.ph && fs.n == st.n && fs.last_c == st.last_c && fs.d0 == st.d0 &&
+                fs.d1 == st.d1 && fs.d2 == st.d2 && fs.d3 == st.d3 && fs.h0 == st.h0 && fs.h1 == st.h1 && fs.h2 == st.h2 &&
+                fs.h3 == st.h3;
+    }
+    v[11] = dns_dnssec(R, 0, len, qd, an, ns, ar);
+    v[12] = dns_first_additional(R, 0, len, qd, an, ns, ar);
+    uint64_t addr = 0;
+    v[13] = dns_ecs(R, 0, len, qd, an, ns, ar, addr);
+    v[14] = addr;
+}
+
+extern "C" {
+// the message must be readable PV_RECS_PAD bytes past len, as every record blob on the device is
+int h_dns_dnssec(const uint8_t *msg, uint32_t len)
+{
+    const HAcc R{msg};
+    return dns_dnssec(R, 0, len, hdr16(msg, len, 4), hdr16(msg, len, 6), hdr16(msg, len, 8), hdr16(msg, len, 10));
+}
+// offset of the first additional record, 0 if none
+uint32_t h_first_additional(const uint8_t *msg, uint32_t len)
+{
+    const HAcc R{msg};
+    return dns_first_additional(R, 0, len, hdr16(msg, len, 4), hdr16(msg, len, 6), hdr16(msg, len, 8), hdr16(msg, len, 10));
+}
+// ECS family (0 none, 1 IPv4, 2 IPv6) and the kept address bytes, little-endian
+uint32_t h_dns_ecs(const uint8_t *msg, uint32_t len, uint64_t *addr)
+{
+    const HAcc R{msg};
+    return dns_ecs(R, 0, len, hdr16(msg, len, 4), hdr16(msg, len, 6), hdr16(msg, len, 8), hdr16(msg, len, 10), *addr);
+}
+void h_dns_all(const uint8_t *msg, uint32_t len, uint64_t *v, char *name, uint32_t *name_n)
+{
+    const HAcc R{msg};
+    dns_all(R, msg, len, v, name, name_n);
+}
+// the same through TrAcc: returns the end of the highest byte read (0: nothing was read)
+uint64_t h_dns_all_tracked(const uint8_t *msg, uint32_t len, uint64_t *v, char *name, uint32_t *name_n)
+{
+    uint64_t hi = 0;
+    const TrAcc R{msg, &hi};
+    dns_all(R, msg, len, v, name, name_n);
+    return hi;
+}
+}
+
 #include <arpa/inet.h>
 
 // PvParams::nets from subnet lists, as pv_host.cpp fills it from a host spec (v4: in_addr.s_addr
