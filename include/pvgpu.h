@@ -435,6 +435,17 @@ int pv_dns_event_seconds(pv_ctx *ctx, const uint8_t *d_recs, const uint32_t *d_o
 int pv_plan_dns_draws(pv_ctx *ctx, uint64_t *draws);
 int pv_sample_skip(pv_ctx *ctx, uint64_t net_draws, uint64_t dns_draws);
 int pv_dns_event_seconds_host(pv_ctx *ctx, const uint8_t *recs, size_t bytes, int64_t *secs, uint32_t max, uint32_t *n);
+/* What the context's BPF program (pv_set_bpf) keeps of a device batch, copied back to host
+ * buffers: the filter exactly as pv_process_device runs it on the batch, and nothing after it (no
+ * handler sees the records, no window changes). kept / kept_cap: the kept records, in order;
+ * offs / offs_cap: their byte offsets; kept_info: the pv_index_info of the kept run (all zero
+ * when nothing is kept); sc_idx / sc_sec / sc_cap: its ts_sec change points, kept_info->
+ * n_sec_changes of them. pad: NULL, or PV_RECS_PAD bytes: what follows the kept records in the
+ * context's buffer, which the kernels after the filter may read (zeros when nothing is kept).
+ * PV_EINVAL when no program is set; PV_ECAPACITY when an output buffer is too small. */
+int pv_bpf_filter_device(pv_ctx *ctx, const uint8_t *d_recs, const uint32_t *d_offs, const pv_index_info *info, uint8_t *kept,
+                         size_t kept_cap, uint32_t *offs, uint32_t offs_cap, pv_index_info *kept_info, uint32_t *sc_idx,
+                         uint32_t *sc_sec, uint32_t sc_cap, uint8_t *pad);
 /* Record cuts of a capture into `world` contiguous shards (cuts[0..world], cuts[world] = n):
  * about equal sizes, each cut at a record boundary that no DNS-over-TCP flow (a TCP packet with
  * a DNS port, keyed as the TCP stage keys it) spans, so DNS over TCP across shard edges matches a

@@ -212,8 +212,9 @@ EXPORTS = ["pv_version", "pv_device_count", "pv_create", "pv_destroy", "pv_last_
            "pv_slow_x_finish", "pv_comm_slow_finish", "pv_geodb_open", "pv_geodb_open_file", "pv_geodb_close",
            "pv_geodb_last_error", "pv_geodb_entries", "pv_geodb_hash", "pv_geodb_hashes", "pv_set_net_filters", "pv_geodb_entry", "pv_geodb_lookup", "pv_set_geodb",
            "pv_set_dns_geo", "pv_dns_geo_timing", "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing", "pv_set_bgp", "pv_bgp_timing", "pv_chain_stats", "pv_fuse_stats",
-           "pv_ring_stats", "pv_set_v2_geo", "pv_set_net2_filters", "pv_v2_geo_timing"]
+           "pv_ring_stats", "pv_set_v2_geo", "pv_set_net2_filters", "pv_v2_geo_timing", "pv_bpf_filter_device"]
 PV_GEODB_CITY, PV_GEODB_ASN = 0, 1
+PV_RECS_PAD = 256  # readable bytes behind a device batch's last record (include/pvgpu.h)
 # pv_allreduce_fn: (uint64_t *buf, size_t n, int op, void *user) -> int
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
 PV_HANDLER_NET, PV_HANDLER_DNS, PV_HANDLER_DHCP, PV_HANDLER_BGP = 1, 2, 4, 8
@@ -406,6 +407,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.pv_v2_geo_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     lib.pv_dns_geo_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     lib.pv_geodb_lookup_device.argtypes = [P, U32, P, ctypes.c_size_t, U32, P]
+    lib.pv_bpf_filter_device.argtypes = [P, P, P, ctypes.POINTER(pv_index_info), P, ctypes.c_size_t, P, U32,
+                                         ctypes.POINTER(pv_index_info), P, P, U32, P]
     lib.pv_set_dhcp.argtypes = [P, ctypes.POINTER(pv_dhcp_config)]
     lib.pv_dhcp_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.c_int]
     lib.pv_set_bgp.argtypes = [P, ctypes.POINTER(pv_bgp_config)]
@@ -994,6 +997,25 @@ class PvHandlers:
         rejects never reach the handlers; [] removes it"""
         self._bpf = bpf_program(insns or [])
         self._check(self.lib.pv_set_bpf(self.ctx, self._bpf, len(insns or [])), "pv_set_bpf")
+
+    def bpf_filter_device(self, d_recs: int, d_offs: int, index: "RecordIndex", with_pad: bool = False):
+        """what the context's program keeps of a device batch (pv_bpf_filter_device: the filter as
+        process_device runs it, no handler fed): (kept_bytes, offsets, info, sc_idx, sc_sec) as
+        RecordIndex holds them; with_pad adds the PV_RECS_PAD bytes behind the kept records"""
+        n = max(1, int(index.info.n_records))
+        kept = np.empty(max(1, int(index.info.bytes_used)), dtype=np.uint8)
+        offs = np.empty(n, dtype=np.uint32)
+        sci = np.empty(n, dtype=np.uint32)
+        scs = np.empty(n, dtype=np.uint32)
+        pad = np.empty(PV_RECS_PAD, dtype=np.uint8) if with_pad else None
+        info = pv_index_info()
+        self._check(self.lib.pv_bpf_filter_device(self.ctx, d_recs, d_offs, ctypes.byref(index.info), kept.ctypes.data,
+                                                  kept.nbytes, offs.ctypes.data, n, ctypes.byref(info), sci.ctypes.data,
+                                                  scs.ctypes.data, n, pad.ctypes.data if with_pad else None),
+                    "pv_bpf_filter_device")
+        out = (kept[: info.bytes_used].tobytes(), offs[: info.n_records], info, sci[: info.n_sec_changes],
+               scs[: info.n_sec_changes])
+        return out + (pad.tobytes(),) if with_pad else out
 
     def _check(self, rc, what):
         if rc:

@@ -3207,6 +3207,9 @@ int bpf_filter_device(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, 
     const uint64_t bytes = (uint64_t)tail[0] + tail[1];
     const uint32_t nk = tail[2] + tail[3];
     if (!nk) return 0;
+    // zeros behind the kept records, as behind every staged batch (an earlier, longer kept run's
+    // bytes lie there otherwise, and the kernels after the filter may read into the padding)
+    if (!hip_ok(e = hipMemsetAsync(c->d_frecs + bytes, 0, PV_RECS_PAD, st))) return c->hipfail(e, "BPF filter");
     hipLaunchKernelGGL(pv_bpf_gather, dim3(grid), dim3(256), 0, st, d_recs, d_offs, n, (const uint32_t *)sz, (const uint32_t *)boff,
                        (const uint32_t *)rank, c->d_frecs, c->d_foffs);
     // the kept run's change points (sz / kf / boff reused: flags, seconds, positions)
@@ -4887,6 +4890,45 @@ int pv_dns_event_seconds(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_off
     const int rc = dns_event_seconds_batch(c, d_recs, d_offs, info, sc_idx, sc_sec, secs, max, n);
     tcp_reset(c);
     return rc;
+}
+
+// What the context's BPF program keeps of a device batch, copied back: bpf_filter_device as
+// pv_process_device runs it, and nothing after it (no handler sees the records).
+int pv_bpf_filter_device(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, const pv_index_info *info, uint8_t *kept,
+                         size_t kept_cap, uint32_t *offs, uint32_t offs_cap, pv_index_info *kept_info, uint32_t *sc_idx,
+                         uint32_t *sc_sec, uint32_t sc_cap, uint8_t *pad)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!info || !kept_info) return c->fail(PV_EINVAL, "pv_bpf_filter_device: bad argument");
+    memset(kept_info, 0, sizeof *kept_info);
+    if (pad) memset(pad, 0, PV_RECS_PAD);
+    if (c->bpf.empty()) return c->fail(PV_EINVAL, "pv_bpf_filter_device: no BPF program set (pv_set_bpf)");
+    if (info->n_records == 0) return 0;
+    if (!d_recs || !d_offs) return c->fail(PV_EINVAL, "pv_bpf_filter_device: bad argument");
+    if (info->n_records > c->max_records) return c->fail(PV_ECAPACITY, "batch of %llu records exceeds max_records %llu",
+                                           (unsigned long long)info->n_records, (unsigned long long)c->max_records);
+    hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    pv_index_info finfo;
+    std::vector<uint32_t> fsci, fscs;
+    if (int rc = bpf_filter_device(c, d_recs, d_offs, info, st, finfo, fsci, fscs)) return rc;
+    if (finfo.n_records == 0) return 0;
+    if (finfo.bytes_used > kept_cap || finfo.n_records > offs_cap || fsci.size() > sc_cap || (finfo.bytes_used && !kept) ||
+        !offs || (!fsci.empty() && (!sc_idx || !sc_sec)))
+        return c->fail(PV_ECAPACITY, "pv_bpf_filter_device: %llu bytes, %llu records, %zu second changes kept: an output buffer is too small",
+                       (unsigned long long)finfo.bytes_used, (unsigned long long)finfo.n_records, fsci.size());
+    hipError_t e;
+    if (!hip_ok(e = hipMemcpyAsync(kept, c->d_frecs, finfo.bytes_used, hipMemcpyDeviceToHost, st)) ||
+        !hip_ok(e = hipMemcpyAsync(offs, c->d_foffs, (size_t)finfo.n_records * 4, hipMemcpyDeviceToHost, st)) ||
+        (pad && !hip_ok(e = hipMemcpyAsync(pad, c->d_frecs + finfo.bytes_used, PV_RECS_PAD, hipMemcpyDeviceToHost, st))) ||
+        !hip_ok(e = hipStreamSynchronize(st)))
+        return c->hipfail(e, "pv_bpf_filter_device: copy back");
+    if (!fsci.empty()) {
+        memcpy(sc_idx, fsci.data(), fsci.size() * 4);
+        memcpy(sc_sec, fscs.data(), fscs.size() * 4);
+    }
+    *kept_info = finfo;
+    return 0;
 }
 
 } // extern "C"

@@ -24,8 +24,19 @@ INVALID = {"empty": [], "no_ret": [(0x28, 0, 0, 12)], "jump_out": [(0x15, 5, 0, 
            "bad_op": [(0xff, 0, 0, 0), (0x6, 0, 0, 0)]}
 
 
-def run(prog, pkt: bytes, wirelen: int) -> int:
-    """bpf_filter(prog, pkt, wirelen, len(pkt))"""
+TRACE_COUNTS = ("edge_pass", "edge_fail", "load_fail", "div0_x", "ind_wrap")
+
+
+def new_trace():
+    return dict({"ops": set()}, **{k: 0 for k in TRACE_COUNTS})
+
+
+def run(prog, pkt: bytes, wirelen: int, trace=None) -> int:
+    """bpf_filter(prog, pkt, wirelen, len(pkt)). trace (new_trace()): collects what the run did, for
+    the conditions of the fuzz (tests/test_bpf_fuzz.py): "ops" the opcodes executed, and counts of
+    "edge_pass" (a load that ends exactly at the capture's end), "edge_fail" (one that ends one byte
+    behind it), "load_fail" (every failed load), "div0_x" (division or modulus by X == 0) and
+    "ind_wrap" (an indexed load with X + k >= 2^32). The answer does not depend on it."""
     a = x = 0
     mem = [0] * 16
     pc = 0
@@ -34,6 +45,8 @@ def run(prog, pkt: bytes, wirelen: int) -> int:
     while True:
         code, jt, jf, k = prog[pc]
         c = code & 7
+        if trace is not None:
+            trace["ops"].add(code)
         if c in (0, 1):
             mode, size = code & 0xE0, code & 0x18
             if mode == 0x00:
@@ -43,12 +56,21 @@ def run(prog, pkt: bytes, wirelen: int) -> int:
             elif mode == 0x60:
                 v = mem[k]
             elif mode == 0xA0:
+                if trace is not None:
+                    trace["edge_pass"] += k + 1 == n
+                    trace["edge_fail"] += k + 1 == n + 1
+                    trace["load_fail"] += k >= n
                 if k >= n:
                     return 0
                 v = (pkt[k] & 0xF) * 4
             else:
                 off = (x if mode == 0x40 else 0) + k
                 w = {0x00: 4, 0x08: 2, 0x10: 1}[size]
+                if trace is not None:
+                    trace["edge_pass"] += off + w == n
+                    trace["edge_fail"] += off + w == n + 1
+                    trace["load_fail"] += off + w > n
+                    trace["ind_wrap"] += mode == 0x40 and off >= 1 << 32
                 if off + w > n:
                     return 0
                 v = int.from_bytes(pkt[off:off + w], "big")
@@ -63,6 +85,8 @@ def run(prog, pkt: bytes, wirelen: int) -> int:
         elif c == 4:
             s = x if code & 8 else k
             op = code & 0xF0
+            if trace is not None and code & 8 and op in (0x30, 0x90):
+                trace["div0_x"] += s == 0
             if op == 0x00:
                 a = (a + s) & m32
             elif op == 0x10:
