@@ -866,6 +866,74 @@ typedef struct pv_bgp_config {
 int pv_set_bgp(pv_ctx *ctx, const pv_bgp_config *cfg);
 /* Device time of pv_bgp_scan, as pv_dhcp_timing gives pv_dhcp_scan's. */
 int pv_bgp_timing(pv_ctx *ctx, double *scan_ms, uint64_t *launches, int reset);
+
+/* ---- The flow handler (FlowStreamHandler, src/handlers/flow, fed by src/inputs/flow): the "flow"
+ * schema, for the three fixed-layout, stateless export formats NetFlow v1, v5 and v7. While it is
+ * attached every batch (after the BPF filter) gets one more device pass (pv_flow_scan: one lane per
+ * record) that finds the flow datagrams: a UDP packet, as the Net pass sees one, to one of the
+ * configured ports (none configured: any UDP packet, the reference's pcap_file mode), whose payload
+ * process_netflow_packet accepts (version 1 / 5 / 7, 1 <= count <= 24 / 30 / 30, length exactly
+ * NFx_PACKET_SIZE(count)). pv_flow_decode writes them as two lists in record order, the datagrams
+ * and their flow records, which the host manager replays: one event per datagram stamped with the
+ * NetFlow header's time (both fields 0: the record's pcap stamp), its own window (shifted by its
+ * own events; pv_set_start_tstamp, pv_set_end_tstamp and pv_check_period_shift reach it), its own
+ * jsf32 deep-sampling draws, devices by exporter address, interfaces by index. The other passes
+ * and their outputs do not change. A batch with more than max_events flow records is decoded in
+ * rounds; nothing is dropped.
+ * Outputs: pv_window_json gains a "flow" object: period, wire_packets.{events, deep_samples} and
+ * devices.<exporter>.{records_flows, records_filtered, top_{in,out}_interfaces_{bytes,packets},
+ * interfaces.<index>.{cardinality.*, {in,out}_{udp_,tcp_,other_l4_,ipv4_,ipv6_,}{bytes,packets},
+ * top_{in,out}_{src,dst}_{ips,ports,ip_ports}_*, top_{in,out}_{dscp,ecn}_*, top_conversations_*}},
+ * gated by the groups as FlowMetricsBucket::to_json gates them; records_filtered is always 0, the
+ * handler's filters are not built.
+ * Not built: NetFlow v9 and IPFIX (template state crosses datagrams; they are counted by
+ * pv_flow_stats, never decoded), sFlow, the filters, enrichment and summarization.
+ * Refused with PV_EUNSUPPORTED and a message naming the flow handler: pv_window_prometheus,
+ * pv_window_opentelemetry and pv_bucket_merge with PV_HANDLER_FLOW; pv_process_dnstap while
+ * attached; sharded runs (pktvisor_amd.dist); the top_geo group with a geo database attached
+ * (without one nothing is counted and top_geo_loc_{bytes,packets} / top_asn_{bytes,packets} are
+ * written as empty lists, as the reference writes them). */
+#define PV_HANDLER_FLOW 16u
+typedef enum pv_flow_group {
+    PV_FLOW_COUNTERS = 1 << 0,
+    PV_FLOW_CARDINALITY = 1 << 1,
+    PV_FLOW_TOP_IPS = 1 << 2,
+    PV_FLOW_TOP_PORTS = 1 << 3,
+    PV_FLOW_TOP_IPS_PORTS = 1 << 4,
+    PV_FLOW_BY_BYTES = 1 << 5,
+    PV_FLOW_BY_PACKETS = 1 << 6,
+    PV_FLOW_CONVERSATIONS = 1 << 7,
+    PV_FLOW_TOP_TOS = 1 << 8,
+    PV_FLOW_TOP_GEO = 1 << 9,
+    PV_FLOW_TOP_INTERFACES = 1 << 10
+} pv_flow_group;
+#define PV_FLOW_MAX_UDP_PORTS 8
+/* One row of the port-name table (IpPort's lists, src/IpPort.cpp): the ports [first, last] of
+ * `protocol` (6 = tcp, 17 = udp) are named `name`. Rows in file order: the first row of a (protocol,
+ * last) pair stays. */
+typedef struct pv_flow_port_name {
+    uint16_t last, first;
+    uint32_t protocol;
+    const char *name;
+} pv_flow_port_name;
+typedef struct pv_flow_config {
+    uint32_t groups;          /* pv_flow_group bits | PV_GROUPS_SET; without PV_GROUPS_SET the reference's defaults */
+    uint32_t n_ports;         /* 0..PV_FLOW_MAX_UDP_PORTS; 0 = any UDP packet */
+    uint16_t ports[PV_FLOW_MAX_UDP_PORTS]; /* UDP destination ports of the flow input */
+    uint32_t recorded_stream; /* "recorded_stream" (period lengths are the stream's either way) */
+    uint32_t max_events;      /* flow records a decode round stores; 0 => min(30 * max_records, 1 << 20) */
+    const pv_flow_port_name *port_names; /* optional: without it ports render as numbers */
+    uint32_t n_port_names;
+} pv_flow_config;
+/* Call before the first batch (or after pv_reset); NULL detaches. Allocates every device buffer of
+ * the stage, so a steady-state batch allocates nothing. */
+int pv_set_flow(pv_ctx *ctx, const pv_flow_config *cfg);
+/* Device time of pv_flow_scan, as pv_dhcp_timing gives pv_dhcp_scan's. */
+int pv_flow_timing(pv_ctx *ctx, double *scan_ms, uint64_t *launches, int reset);
+/* out[0]: datagrams accepted; out[1]: UDP payloads on a configured port that were refused (the
+ * reference input's packet_errors); out[2]: those among them whose version field is 9 or 10. Summed
+ * since the handler was attached or pv_reset. */
+int pv_flow_stats(pv_ctx *ctx, uint64_t out[3]);
 /* pv_geodb_hash of the attached city and ASN databases (0: none): what the ranks of a sharded run
  * compare before they sum their windows. pv_comm_allreduce_window compares them itself; a caller
  * that moves the pv_window_regions words with its own transport compares these first. */

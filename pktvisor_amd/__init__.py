@@ -84,6 +84,16 @@ class pv_bgp_config(ctypes.Structure):
     _fields_ = [("recorded_stream", ctypes.c_uint32), ("max_events", ctypes.c_uint32)]
 
 
+class pv_flow_port_name(ctypes.Structure):
+    _fields_ = [("last", ctypes.c_uint16), ("first", ctypes.c_uint16), ("protocol", ctypes.c_uint32), ("name", ctypes.c_char_p)]
+
+
+class pv_flow_config(ctypes.Structure):
+    _fields_ = [("groups", ctypes.c_uint32), ("n_ports", ctypes.c_uint32), ("ports", ctypes.c_uint16 * 8),
+                ("recorded_stream", ctypes.c_uint32), ("max_events", ctypes.c_uint32),
+                ("port_names", ctypes.POINTER(pv_flow_port_name)), ("n_port_names", ctypes.c_uint32)]
+
+
 from pktvisor_amd.config import ConfigException as ConfigError  # noqa: E402  (the reference's texts)
 from pktvisor_amd.config import StreamHandlerException  # noqa: E402,F401
 
@@ -211,14 +221,15 @@ EXPORTS = ["pv_version", "pv_device_count", "pv_create", "pv_destroy", "pv_last_
            "pv_topn_x_candidates", "pv_topn_x_names", "pv_topn_x_view", "pv_values_x_select", "pv_comm_values_select",
            "pv_slow_x_finish", "pv_comm_slow_finish", "pv_geodb_open", "pv_geodb_open_file", "pv_geodb_close",
            "pv_geodb_last_error", "pv_geodb_entries", "pv_geodb_hash", "pv_geodb_hashes", "pv_set_net_filters", "pv_geodb_entry", "pv_geodb_lookup", "pv_set_geodb",
-           "pv_set_dns_geo", "pv_dns_geo_timing", "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing", "pv_set_bgp", "pv_bgp_timing", "pv_chain_stats", "pv_fuse_stats",
+           "pv_set_dns_geo", "pv_dns_geo_timing", "pv_geodb_lookup_device", "pv_set_dhcp", "pv_dhcp_timing", "pv_set_bgp", "pv_bgp_timing", "pv_set_flow", "pv_flow_timing", "pv_flow_stats", "pv_chain_stats", "pv_fuse_stats",
            "pv_ring_stats", "pv_set_v2_geo", "pv_set_net2_filters", "pv_v2_geo_timing", "pv_bpf_filter_device"]
 PV_GEODB_CITY, PV_GEODB_ASN = 0, 1
 PV_RECS_PAD = 256  # readable bytes behind a device batch's last record (include/pvgpu.h)
 # pv_allreduce_fn: (uint64_t *buf, size_t n, int op, void *user) -> int
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p)
-PV_HANDLER_NET, PV_HANDLER_DNS, PV_HANDLER_DHCP, PV_HANDLER_BGP = 1, 2, 4, 8
-_HANDLER_BITS = {"net": PV_HANDLER_NET, "dns": PV_HANDLER_DNS, "dhcp": PV_HANDLER_DHCP, "bgp": PV_HANDLER_BGP}
+PV_HANDLER_NET, PV_HANDLER_DNS, PV_HANDLER_DHCP, PV_HANDLER_BGP, PV_HANDLER_FLOW = 1, 2, 4, 8, 16
+_HANDLER_BITS = {"net": PV_HANDLER_NET, "dns": PV_HANDLER_DNS, "dhcp": PV_HANDLER_DHCP, "bgp": PV_HANDLER_BGP,
+                 "flow": PV_HANDLER_FLOW}
 PV_PERIOD_AUTO = 0xFFFFFFFF
 PART_NET, PART_DNS = 0, 1
 PV_REDUCE_SUM, PV_REDUCE_MIN = 0, 1
@@ -411,6 +422,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                          ctypes.POINTER(pv_index_info), P, P, U32, P]
     lib.pv_set_dhcp.argtypes = [P, ctypes.POINTER(pv_dhcp_config)]
     lib.pv_dhcp_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.c_int]
+    lib.pv_set_flow.argtypes = [P, ctypes.POINTER(pv_flow_config)]
+    lib.pv_flow_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.c_int]
+    lib.pv_flow_stats.argtypes = [P, ctypes.POINTER(U64)]
     lib.pv_set_bgp.argtypes = [P, ctypes.POINTER(pv_bgp_config)]
     lib.pv_bgp_timing.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.c_int]
     if hasattr(lib, "pv_chain_stats"):  # (diagnostics only: a PVGPU_LIB build of an older tree, for A/B runs, has none)
@@ -741,8 +755,14 @@ class PvHandlers:
                  deep_sample_rate: int = 100, tcp_packet_reassembly_cache_limit: int = 0, bpf=None,
                  tcp_exact_lru: bool = False, geo_city_db=None, geo_asn_db=None, dhcp_config: Optional[dict] = None,
                  dhcp_max_events: int = 0, bgp_config: Optional[dict] = None, bgp_max_events: int = 0,
-                 dns_geo: bool = False, v2_geo: bool = False):
-        """v2_geo: the v2 handlers read the attached databases (pv_set_v2_geo). Net v2: with its top_geo
+                 dns_geo: bool = False, v2_geo: bool = False, flow_config: Optional[dict] = None, flow_max_events: int = 0,
+                 flow_port_csv: Optional[str] = None):
+        """flow_config: attaches the flow handler ("flow" schema, FlowStreamHandler; NetFlow v1 / v5 / v7) with
+        its config map (enable / disable, recorded_stream, sample_rate_scaling, the window keys, and this
+        package's "ports": the UDP destination ports of the flow input, none = any UDP packet);
+        flow_max_events: the flow records one decode round stores (0: the default); flow_port_csv: the path
+        of an IANA-style CSV (Service Name, Port Number, Transport Protocol) that names the ports.
+        v2_geo: the v2 handlers read the attached databases (pv_set_v2_geo). Net v2: with its top_geo
         group, top_geo_loc_packets / top_asn_packets per direction, and the four geo filter keys of
         net2_config as the handler's own filters matched on the device (pv_set_net2_filters). DNS v2:
         with its top_ecs group, top_geo_loc_ecs_xacts / top_asn_ecs_xacts per transaction direction,
@@ -783,10 +803,15 @@ class PvHandlers:
                 xact_ttl_ms = d2["xact_ttl_ms"]
         dhcp = pvcfg.dhcp_start(dict(dhcp_config)) if dhcp_config is not None else None
         bgp = pvcfg.bgp_start(dict(bgp_config)) if bgp_config is not None else None
+        flow = pvcfg.flow_start(dict(flow_config)) if flow_config is not None else None
+        flow_rows = []
+        if flow is not None and flow_port_csv is not None:
+            with open(flow_port_csv, "r", encoding="latin-1", newline="") as fh:
+                flow_rows = pvcfg.iana_port_rows(fh.read())
         if net_config is not None or dns_config is not None or net2_config is not None or dns2_config is not None:
             ncfg, dcfg = dict(net_config or {}), dict(dns_config or {})
             win = pvcfg.window_config([ncfg, dcfg, dict(net2_config or {}), dict(dns2_config or {}), dict(dhcp_config or {}),
-                                       dict(bgp_config or {})])
+                                       dict(bgp_config or {}), dict(flow_config or {})])
             deep_sample_rate = win.get("deep_sample_rate", deep_sample_rate)
             num_periods = win.get("num_periods", num_periods)
             topn_count = win.get("topn_count", topn_count)
@@ -806,9 +831,9 @@ class PvHandlers:
                 self.dnstap_mask = d["dnstap_mask"]
             if d["xact_ttl_ms"] is not None and dns2_config is None:
                 xact_ttl_ms = d["xact_ttl_ms"]
-        elif dhcp_config is not None or bgp_config is not None:
-            # the DHCP / BGP handlers alone carry window keys: the other handlers keep their keyword form
-            win = pvcfg.window_config([dict(dhcp_config or {}), dict(bgp_config or {})])
+        elif dhcp_config is not None or bgp_config is not None or flow_config is not None:
+            # the DHCP / BGP / flow handlers alone carry window keys: the other handlers keep their keyword form
+            win = pvcfg.window_config([dict(dhcp_config or {}), dict(bgp_config or {}), dict(flow_config or {})])
             deep_sample_rate = win.get("deep_sample_rate", deep_sample_rate)
             num_periods = win.get("num_periods", num_periods)
             topn_count = win.get("topn_count", topn_count)
@@ -879,6 +904,39 @@ class PvHandlers:
         self.bgp_attached = False
         if bgp is not None:
             self.set_bgp(bgp["recorded_stream"], bgp_max_events)
+        self.flow_attached = False
+        if flow is not None:
+            self.set_flow(flow["groups"], flow["ports"], flow["recorded_stream"], flow_max_events, flow_rows)
+
+    def set_flow(self, groups: int = 0, ports=(), recorded_stream: bool = False, max_events: int = 0, port_names=()):
+        """attach the flow handler (pv_set_flow): window_json then carries "flow". Before the first batch.
+        groups: pv_flow_group bits | PV_GROUPS_SET (0: the defaults); port_names: rows (last, first,
+        protocol number, name) as config.iana_port_rows gives them."""
+        cfg = pv_flow_config(int(groups), len(ports))
+        for k, p in enumerate(ports):
+            cfg.ports[k] = int(p)
+        cfg.recorded_stream, cfg.max_events = int(bool(recorded_stream)), int(max_events)
+        rows = (pv_flow_port_name * max(1, len(port_names)))()
+        for k, (last, first, proto, name) in enumerate(port_names):
+            rows[k] = pv_flow_port_name(int(last), int(first), int(proto), name.encode("latin-1"))
+        if port_names:
+            cfg.port_names, cfg.n_port_names = ctypes.cast(rows, ctypes.POINTER(pv_flow_port_name)), len(port_names)
+        self._check(self.lib.pv_set_flow(self.ctx, ctypes.byref(cfg)), "pv_set_flow")
+        self.flow_attached = True
+
+    def flow_timing(self, reset: bool = False):
+        """(ms, launches) of pv_flow_scan over the batches processed while set_kernel_timing is on"""
+        ms, n = ctypes.c_double(), ctypes.c_uint64()
+        self._check(self.lib.pv_flow_timing(self.ctx, ctypes.byref(ms), ctypes.byref(n), int(reset)), "pv_flow_timing")
+        return ms.value, n.value
+
+    def flow_stats(self) -> dict:
+        """the flow input's counts since the handler was attached (pv_flow_stats): datagrams accepted, UDP
+        payloads on a configured port refused (the reference input's packet_errors), those of them with a
+        version field of 9 or 10 (NetFlow v9 / IPFIX: counted, never decoded)"""
+        out = (ctypes.c_uint64 * 3)()
+        self._check(self.lib.pv_flow_stats(self.ctx, out), "pv_flow_stats")
+        return {"datagrams": int(out[0]), "invalid": int(out[1]), "invalid_v9_v10": int(out[2])}
 
     def set_bgp(self, recorded_stream: bool = False, max_events: int = 0):
         """attach the BGP handler (pv_set_bgp): window_json then carries "bgp". Before the first batch."""
@@ -1430,6 +1488,7 @@ def last_record_ts(recs: bytes, index: RecordIndex, ts_nano: int = 0):
 
 def pktvisor_reader(path: str, host_spec: Optional[str] = None, periods: int = 5, **kw) -> dict:
     """GPU equivalent of `pktvisor-reader [-H host_spec] --periods N FILE` for net + dns.
+    flow_config=... (with flow_max_events / flow_port_csv): the flow handler over the file's NetFlow datagrams.
     dns_geo=True (with geo_city_db / geo_asn_db): the DNS handler's half of the databases, as PvHandlers takes it.
     v2_geo=True: the v2 handlers' half (Net v2 and DNS v2 geo tops per direction, their geo filters)."""
     linktype, ts_nano, recs = read_pcap(path)

@@ -194,6 +194,106 @@ def bgp_start(cfg: dict) -> dict:
     return {"recorded_stream": "recorded_stream" in cfg}
 
 
+# the flow handler (src/handlers/flow/FlowStreamHandler.h:384-412; defaults FlowStreamHandler.cpp:95-101);
+# "ports" is this package's own key: the UDP destination ports of the flow input
+FLOW_CONFIG_DEFS = ("device_map", "enrichment", "only_device_interfaces", "only_ips", "only_ports", "only_directions",
+                    "geoloc_notfound", "asn_notfound", "summarize_ips_by_asn", "subnets_for_summarization",
+                    "exclude_asns_from_summarization", "exclude_unknown_asns_from_summarization",
+                    "exclude_ips_from_summarization", "sample_rate_scaling", "recorded_stream")
+FLOW_OWN_CONFIG_DEFS = ("ports",)
+# group name -> pv_flow_group bit (include/pvgpu.h)
+FLOW_GROUP_DEFS = {"by_bytes": 1 << 5, "by_packets": 1 << 6, "cardinality": 1 << 1, "conversations": 1 << 7,
+                   "counters": 1 << 0, "top_geo": 1 << 9, "top_interfaces": 1 << 10, "top_ips": 1 << 2,
+                   "top_ips_ports": 1 << 4, "top_ports": 1 << 3, "top_tos": 1 << 8}
+FLOW_DEFAULT_GROUPS = ("counters", "cardinality", "top_ips", "top_ports", "top_ips_ports", "by_bytes", "by_packets")
+FLOW_NOT_BUILT = ("device_map", "enrichment", "only_device_interfaces", "only_ips", "only_ports", "only_directions",
+                  "geoloc_notfound", "asn_notfound", "summarize_ips_by_asn", "subnets_for_summarization",
+                  "exclude_asns_from_summarization", "exclude_unknown_asns_from_summarization",
+                  "exclude_ips_from_summarization")
+FLOW_MAX_PORTS = 8
+
+
+def flow_start(cfg: dict) -> dict:
+    """FlowStreamHandler::start (src/handlers/flow/FlowStreamHandler.cpp:86-269) up to the signal
+    wiring: {"groups": bits | GROUPS_SET, "recorded_stream": bool, "ports": [int]}. The filters,
+    enrichment and summarization are not built: their keys raise. sample_rate_scaling is sFlow's
+    (:352) and has no effect on NetFlow."""
+    cfg = dict(cfg)
+    ports = cfg.pop("ports", [])
+    validate_configs(cfg, FLOW_CONFIG_DEFS)
+    groups = process_groups(cfg, FLOW_GROUP_DEFS, FLOW_DEFAULT_GROUPS)
+    for k in FLOW_NOT_BUILT:
+        if k in cfg:
+            raise ConfigException(f"{k} is not supported by the GPU flow handler")
+    if "sample_rate_scaling" in cfg:
+        _bool(cfg, "sample_rate_scaling")
+    if not isinstance(ports, (list, tuple)) or not all(isinstance(p, int) and not isinstance(p, bool) and 0 <= p <= 65535
+                                                       for p in ports):
+        raise ConfigException("wrong type for key: ports")
+    if len(ports) > FLOW_MAX_PORTS:
+        raise ConfigException(f"ports: at most {FLOW_MAX_PORTS} UDP ports")
+    return {"groups": groups | GROUPS_SET, "recorded_stream": "recorded_stream" in cfg, "ports": [int(p) for p in ports]}
+
+
+def iana_port_rows(text: str) -> list:
+    """IpPort::set_csv_iana_ports (src/IpPort.cpp:34-69) over the text of an IANA-style CSV: the rows
+    (last, first, protocol number, name) in file order. The reference's reader splits at every comma
+    (no quoting), trims blanks and tabs, and wants as many columns in a row as the header has; a row
+    that fails (a column count, a port that is no number) is dropped together with the line after
+    it (the handler's in.next_line())."""
+    lines = text.split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    if not lines:
+        return []
+
+    def cols(line):
+        return [c.strip(" \t") for c in line.rstrip("\r").split(",")]
+
+    header = cols(lines[0])
+    try:
+        want = [header.index(n) for n in ("Service Name", "Port Number", "Transport Protocol")]
+    except ValueError:
+        raise ConfigException("flow_port_csv: missing a column of Service Name, Port Number, Transport Protocol")
+
+    def number(txt):
+        # std::stoul: leading blanks, an optional sign, then digits; what follows is ignored
+        t = txt.lstrip(" \t\n\v\f\r")
+        neg = t[:1] == "-"
+        if t[:1] in "+-":
+            t = t[1:]
+        k = 0
+        while k < len(t) and t[k].isdigit() and t[k].isascii():
+            k += 1
+        if k == 0:
+            raise ValueError(txt)
+        v = int(t[:k])
+        if v >= 1 << 64:
+            raise ValueError(txt)
+        return ((-v if neg else v) & 0xFFFFFFFFFFFFFFFF) & 0xFFFF
+
+    rows = []
+    i = 1
+    while i < len(lines):
+        c = cols(lines[i])
+        i += 1
+        try:
+            if len(c) != len(header):
+                raise ValueError("columns")
+            service, ports, proto = (c[k] for k in want)
+            if not service or not ports or proto not in ("tcp", "udp"):
+                continue
+            cut = ports.find("-")
+            if cut >= 0:
+                first, last = number(ports[:cut]), number(ports[cut + 1:])
+            else:
+                first = last = number(ports)
+            rows.append((last, first, 6 if proto == "tcp" else 17, service))
+        except ValueError:
+            i += 1  # the handler's in.next_line(): the line after a bad row goes too
+    return rows
+
+
 # Net v2 (src/handlers/net/v2/NetStreamHandler.h:25-31,262-267; defaults :47-52)
 NET2_GROUP_DEFS = {"cardinality": 1 << 1, "counters": 1 << 0, "quantiles": 1 << 2, "top_geo": 1 << 3, "top_ips": 1 << 4}
 NET2_DEFAULT_GROUPS = ("counters", "cardinality", "quantiles", "top_geo", "top_ips")

@@ -184,6 +184,7 @@ int ensure_started(pv_ctx *c, int64_t sec, int64_t nsec)
     // not its first DHCP packet)
     if (c->dhcp) c->dhcp->set_start(sec, nsec);
     if (c->bgp) c->bgp->set_start(sec, nsec);
+    if (c->flow) c->flow->set_start(sec, nsec);
     c->started = true;
     return 0;
 }
@@ -261,6 +262,7 @@ void mark_merged(pv_ctx *c, const char *by)
 } // namespace pvh
 static void dhcp_free(pv_ctx *c);
 static void bgp_free(pv_ctx *c);
+static void flow_free(pv_ctx *c);
 static int merged_refuse(pv_ctx *c)
 {
     if (!c->merged) return 0;
@@ -328,6 +330,8 @@ int pv_set_geodb(pv_ctx *c, const pv_geodb *city, const pv_geodb *asn)
     if (!c) return PV_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (c->records_seen) return c->fail(PV_EINVAL, "the geo databases must be set before the first batch");
+    if (c->flow && (c->flow->groups() & PV_FLOW_TOP_GEO) && (city || asn))
+        return c->fail(PV_EUNSUPPORTED, "geo databases: the flow handler's top_geo group is not built");
     const pv_geodb *dbs[2] = {city, asn};
     for (uint32_t k = 0; k < 2; k++)
         if (dbs[k] && dbs[k]->kind != k)
@@ -1029,6 +1033,7 @@ void pv_destroy(pv_ctx *c)
     for (void *p : ptrs) if (p) hipFree(p);
     dhcp_free(c);
     bgp_free(c);
+    flow_free(c);
     for (void *p : {(void *)c->d_nf_pass[0], (void *)c->d_nf_pass[1], (void *)c->d_gfilt}) if (p) hipFree(p);
     for (void *p : {(void *)c->d_nf2_pass[0], (void *)c->d_nf2_pass[1], (void *)c->d_gfilt2}) if (p) hipFree(p);
     for (auto &g : c->geo) {
@@ -1105,6 +1110,10 @@ int pv_reset(pv_ctx *c)
     c->started = c->ended = false;
     if (c->dhcp) c->dhcp->reset();
     if (c->bgp) c->bgp->reset();
+    if (c->flow) {
+        c->flow->reset();
+        c->flow_stats[0] = c->flow_stats[1] = c->flow_stats[2] = 0;
+    }
     c->records_seen = 0;
     c->seen_hi = 0; // (every slot is cleared before its next use: no entry keeps a seen flag)
     c->seen_off = false;
@@ -3358,6 +3367,150 @@ extern "C" int pv_dhcp_timing(pv_ctx *c, double *scan_ms, uint64_t *launches, in
     return 0;
 }
 
+// The flow handler's device stage on a batch (pv_flow.hip) and the host replay of what it finds:
+// the scan's per-tile masks and four count arrays, one exclusive scan over all four (each tile's
+// rank bases, each array's total), then rounds of at most flow_cap flow records, each datagram
+// whole (pv_flow.h): decode, copy back, replay in record order. Nothing is dropped. A batch that
+// fits one round takes one synchronize after the decode; a longer one reads where the next round
+// begins first. The caller holds c->mu.
+static int flow_stage(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, const pv_index_info *info, hipStream_t st)
+{
+    hipError_t e;
+    const uint32_t n = (uint32_t)info->n_records, ntiles = (n + 63) / 64, nscan = 4 * ntiles + 1;
+    size_t tb = 0;
+    if (!hip_ok(e = pv_exclusive_scan_u32(nullptr, &tb, nullptr, nullptr, nscan, st))) return c->hipfail(e, "flow scan size");
+    if (int rc = x_grow_dev(c, &c->d_fl_scan, c->fl_scan_bytes, tb, "flow scan")) return rc;
+    const uint32_t grid = std::max(1u, std::min((ntiles + 3) / 4, (uint32_t)c->cus * 8));
+    const bool timed = c->timing_every != 0;
+    if (timed) hipEventRecord(c->ev_start, st);
+    hipLaunchKernelGGL(pv_flow_scan, dim3(grid), dim3(256), 0, st, d_recs, d_offs, n, c->cfg.linktype, c->cfg.ts_nano,
+                       (const PvParams *)c->d_fl_params, c->flow_ports, c->d_fl_mask, c->d_fl_tile);
+    if (!hip_ok(e = hipGetLastError())) return c->hipfail(e, "launch pv_flow_scan");
+    if (timed) hipEventRecord(c->ev_stop, st);
+    tb = c->fl_scan_bytes;
+    uint32_t tot[5] = {0, 0, 0, 0, 0}; // the scan at each array's start and at the closing entry
+    if (!hip_ok(e = pv_exclusive_scan_u32(c->d_fl_scan, &tb, c->d_fl_tile, c->d_fl_rank, nscan, st))) return c->hipfail(e, "flow scan");
+    for (uint32_t k = 1; k <= 4; k++)
+        if (!hip_ok(e = hipMemcpyAsync(&tot[k], c->d_fl_rank + (size_t)k * ntiles, 4, hipMemcpyDeviceToHost, st)))
+            return c->hipfail(e, "flow scan");
+    if (!hip_ok(e = hipStreamSynchronize(st))) return c->hipfail(e, "flow scan");
+    if (timed) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->ev_start, c->ev_stop) == hipSuccess) { c->flow_scan_ms += ms; c->flow_scan_launches++; }
+    }
+    const uint32_t ndgram = tot[1], nrec = tot[2] - tot[1];
+    c->flow_stats[0] += ndgram;
+    c->flow_stats[1] += tot[3] - tot[2];
+    c->flow_stats[2] += tot[4] - tot[3];
+    uint32_t dbase = 0, fbase = 0;
+    while (fbase < nrec) {
+        const bool last = (uint64_t)fbase + c->flow_cap >= nrec;
+        hipLaunchKernelGGL(pv_flow_decode, dim3(grid), dim3(256), 0, st, d_recs, d_offs, n, c->cfg.linktype, c->cfg.ts_nano,
+                           (const PvParams *)c->d_fl_params, c->flow_ports, (const unsigned long long *)c->d_fl_mask,
+                           (const uint32_t *)c->d_fl_tile, (const uint32_t *)c->d_fl_rank, dbase, fbase, c->flow_cap, c->flow_pcap,
+                           nrec, c->d_fl_pk, c->d_fl_fr, c->d_fl_next);
+        if (!hip_ok(e = hipGetLastError())) return c->hipfail(e, "launch pv_flow_decode");
+        uint32_t next[2] = {ndgram, nrec};
+        if (!last && (!hip_ok(e = hipMemcpyAsync(next, c->d_fl_next, 8, hipMemcpyDeviceToHost, st)) || !hip_ok(e = hipStreamSynchronize(st))))
+            return c->hipfail(e, "flow round");
+        if (next[0] <= dbase || next[0] > ndgram || next[1] <= fbase || next[1] > nrec || next[0] - dbase > c->flow_pcap ||
+            next[1] - fbase > c->flow_cap + PV_FLOW_SLACK)
+            return c->fail(PV_EINVAL, "flow decode: a round ends at datagram %u, record %u", next[0], next[1]); // (not reached)
+        const uint32_t kd = next[0] - dbase, kr = next[1] - fbase;
+        c->h_fl_pk.resize(kd);
+        c->h_fl_fr.resize(kr);
+        if (!hip_ok(e = hipMemcpyAsync(c->h_fl_pk.data(), c->d_fl_pk, (size_t)kd * sizeof(PvFlowPacket), hipMemcpyDeviceToHost, st)) ||
+            !hip_ok(e = hipMemcpyAsync(c->h_fl_fr.data(), c->d_fl_fr, (size_t)kr * sizeof(PvFlowRecord), hipMemcpyDeviceToHost, st)) ||
+            !hip_ok(e = hipStreamSynchronize(st)))
+            return c->hipfail(e, "flow records");
+        c->flow->replay(c->h_fl_pk.data(), kd, c->h_fl_fr.data(), kr, fbase);
+        dbase = next[0];
+        fbase = next[1];
+    }
+    return 0;
+}
+
+static void flow_free(pv_ctx *c)
+{
+    for (void *p : {(void *)c->d_fl_mask, (void *)c->d_fl_tile, (void *)c->d_fl_rank, (void *)c->d_fl_next, (void *)c->d_fl_pk,
+                    (void *)c->d_fl_fr, (void *)c->d_fl_params, c->d_fl_scan})
+        if (p) hipFree(p);
+    c->d_fl_mask = nullptr;
+    c->d_fl_tile = c->d_fl_rank = c->d_fl_next = nullptr;
+    c->d_fl_pk = nullptr;
+    c->d_fl_fr = nullptr;
+    c->d_fl_params = nullptr;
+    c->d_fl_scan = nullptr;
+    c->fl_scan_bytes = 0;
+    c->flow.reset();
+}
+
+// FlowStreamHandler's constructor and start() (FlowStreamHandler.cpp:72-269) on this context's
+// records: the manager with the context's window config, and every device buffer of the stage
+extern "C" int pv_set_flow(pv_ctx *c, const pv_flow_config *cfg)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    if (c->started) return c->fail(PV_EINVAL, "pv_set_flow: call before the first batch");
+    hipSetDevice(c->device);
+    flow_free(c);
+    if (!cfg) return 0;
+    if (cfg->n_ports > PV_FLOW_MAX_UDP_PORTS) return c->fail(PV_EINVAL, "pv_set_flow: at most %d ports", PV_FLOW_MAX_UDP_PORTS);
+    if (cfg->n_port_names && !cfg->port_names) return c->fail(PV_EINVAL, "pv_set_flow: n_port_names without port_names");
+    // the default groups (FlowStreamHandler.cpp:95-101)
+    const uint32_t groups = (cfg->groups & PV_GROUPS_SET) ? (cfg->groups & 0x7ffu)
+                                                          : (uint32_t)(PV_FLOW_COUNTERS | PV_FLOW_CARDINALITY | PV_FLOW_TOP_IPS | PV_FLOW_TOP_PORTS |
+                                                                       PV_FLOW_TOP_IPS_PORTS | PV_FLOW_BY_BYTES | PV_FLOW_BY_PACKETS);
+    if ((groups & PV_FLOW_TOP_GEO) && (c->geo[0].on || c->geo[1].on))
+        return c->fail(PV_EUNSUPPORTED, "pv_set_flow: the flow handler's top_geo group is not built (a geo database is attached)");
+    const uint64_t maxn = std::max<uint64_t>(1, c->max_records);
+    // (32-bit ranks: every batch has fewer than 2^32 flow records and scan entries)
+    if (maxn > (1ull << 26)) return c->fail(PV_EINVAL, "pv_set_flow: max_records above 2^26");
+    const uint64_t cap = cfg->max_events ? std::min<uint64_t>(cfg->max_events, 1u << 24) : std::min<uint64_t>(maxn * PV_FLOW_MAXFLOWS, 1u << 20);
+    c->flow_cap = (uint32_t)cap;
+    c->flow_pcap = (uint32_t)std::min<uint64_t>(cap, maxn);
+    c->flow_ports = PvFlowPorts{};
+    c->flow_ports.n = cfg->n_ports;
+    for (uint32_t k = 0; k < cfg->n_ports; k++) c->flow_ports.port[k] = cfg->ports[k];
+    std::vector<pvflow::PortRow> rows;
+    for (uint32_t k = 0; k < cfg->n_port_names; k++) {
+        const pv_flow_port_name &r = cfg->port_names[k];
+        if ((r.protocol != 6 && r.protocol != 17) || !r.name) return c->fail(PV_EINVAL, "pv_set_flow: port name row %u", k);
+        rows.push_back({r.last, r.first, (uint8_t)(r.protocol == 17), r.name});
+    }
+    const size_t ntiles = (size_t)((maxn + 63) / 64), nscan = 4 * ntiles + 1;
+    hipError_t e;
+    size_t tb = 0;
+    if (!hip_ok(e = hipMalloc(&c->d_fl_mask, ntiles * 8)) || !hip_ok(e = hipMalloc(&c->d_fl_tile, nscan * 4)) ||
+        !hip_ok(e = hipMalloc(&c->d_fl_rank, nscan * 4)) || !hip_ok(e = hipMalloc(&c->d_fl_next, 256)) ||
+        !hip_ok(e = hipMalloc(&c->d_fl_pk, (size_t)c->flow_pcap * sizeof(PvFlowPacket))) ||
+        !hip_ok(e = hipMalloc(&c->d_fl_fr, ((size_t)cap + PV_FLOW_SLACK) * sizeof(PvFlowRecord))) ||
+        !hip_ok(e = hipMalloc(&c->d_fl_params, sizeof(PvParams))) || !hip_ok(e = hipMemset(c->d_fl_params, 0, sizeof(PvParams))) ||
+        !hip_ok(e = pv_exclusive_scan_u32(nullptr, &tb, nullptr, nullptr, nscan, c->stream))) {
+        flow_free(c);
+        return c->hipfail(e, "flow stage buffers");
+    }
+    if (int rc = x_grow_dev(c, &c->d_fl_scan, c->fl_scan_bytes, tb, "flow scan")) { flow_free(c); return rc; }
+    c->flow.reset(new pvflow::Manager(c->cfg.num_periods, c->cfg.deep_sample_rate, groups, rows));
+    c->flow_stats[0] = c->flow_stats[1] = c->flow_stats[2] = 0;
+    return 0;
+}
+
+extern "C" int pv_flow_timing(pv_ctx *c, double *scan_ms, uint64_t *launches, int reset)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    if (scan_ms) *scan_ms = c->flow_scan_ms;
+    if (launches) *launches = c->flow_scan_launches;
+    if (reset) { c->flow_scan_ms = 0; c->flow_scan_launches = 0; }
+    return 0;
+}
+
+extern "C" int pv_flow_stats(pv_ctx *c, uint64_t out[3])
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int k = 0; k < 3; k++) out[k] = c->flow_stats[k];
+    return 0;
+}
+
 extern "C" int pv_fuse_stats(pv_ctx *c, uint64_t out[2], int reset)
 {
     std::lock_guard<std::mutex> g(c->mu);
@@ -3564,6 +3717,10 @@ int pv_process_device(pv_ctx *c, const uint8_t *d_recs, const uint32_t *d_offs, 
     if (c->bgp) {
         // the BGP handler's own pass, as independent of the others
         if (int rc = bgp_stage(c, d_recs, d_offs, info, st)) return rc;
+    }
+    if (c->flow) {
+        // and the flow handler's
+        if (int rc = flow_stage(c, d_recs, d_offs, info, st)) return rc;
     }
     std::vector<Shift> nsh, dsh;
     if (int rc = batch_shifts(c, d_recs, d_offs, info, sc_idx, sc_sec, st, nsh, dsh)) return rc;
@@ -3951,6 +4108,8 @@ int pv_process_dnstap(pv_ctx *c, const uint8_t *buf, size_t bytes, uint32_t msg_
     if (c->dhcp) return c->fail(PV_EUNSUPPORTED, "DhcpStreamHandler: unsupported input event proxy dnstap (the DHCP handler is attached)");
     // and so does BgpStreamHandler's (BgpStreamHandler.cpp:10-19)
     if (c->bgp) return c->fail(PV_EUNSUPPORTED, "BgpStreamHandler: unsupported input event proxy dnstap (the BGP handler is attached)");
+    // and FlowStreamHandler's takes a flow input only (FlowStreamHandler.cpp:72-84)
+    if (c->flow) return c->fail(PV_EUNSUPPORTED, "FlowStreamHandler: unsupported input event proxy dnstap (the flow handler is attached)");
     hipSetDevice(c->device);
     std::vector<pvi::DtMessage> msgs;
     uint32_t frames = 0;
@@ -4676,6 +4835,7 @@ int pv_set_end_tstamp(pv_ctx *c, int64_t sec, int64_t nsec)
     c->dns.meta[c->dns.slots.front()].set_read_only(sec, nsec);
     if (c->dhcp) c->dhcp->set_end(sec, nsec);
     if (c->bgp) c->bgp->set_end(sec, nsec);
+    if (c->flow) c->flow->set_end(sec, nsec);
     c->ended = true;
     return 0;
 }
@@ -4700,6 +4860,7 @@ int pv_check_period_shift(pv_ctx *c, int64_t sec, int64_t nsec)
     }
     if (c->dhcp) c->dhcp->check_period_shift(sec, nsec);
     if (c->bgp) c->bgp->check_period_shift(sec, nsec);
+    if (c->flow) c->flow->check_period_shift(sec, nsec);
     if (sec < c->dns.next_shift_sec) return 0;
     return dns_period_shift(c, sec, nsec);
 }

@@ -44,6 +44,8 @@
 #include "pv_layout.h"
 #include "pv_dhcp.h"
 #include "pv_bgp.h"
+#include "pv_cpc.h"
+#include "pv_flow.h"
 
 // The kernel's name fingerprint (pv_parse.h NameStats + fp56), compiled for the host so
 // pv_set_dns_filters can key "only_qname" names exactly as the DNS pass keys first-query names.
@@ -180,6 +182,13 @@ extern "C" __global__ void pv_bpf_secs(const uint8_t *out, const uint32_t *ooffs
 extern "C" __global__ void pv_bpf_secs_compact(const uint32_t *flag, const uint32_t *pos, const uint32_t *sec, uint32_t nk, uint32_t cap,
                                                uint32_t *sci, uint32_t *scs);
 extern "C" hipError_t pv_exclusive_scan_u32(void *tmp, size_t *tmp_bytes, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s);
+// the flow handler's device stage (pv_flow.hip)
+extern "C" __global__ void pv_flow_scan(const uint8_t *recs, const uint32_t *offs, uint32_t n, uint32_t linktype, uint32_t ts_nano,
+                                        const PvParams *P, PvFlowPorts L, unsigned long long *mask, uint32_t *tile);
+extern "C" __global__ void pv_flow_decode(const uint8_t *recs, const uint32_t *offs, uint32_t n, uint32_t linktype, uint32_t ts_nano,
+                                          const PvParams *P, PvFlowPorts L, const unsigned long long *mask, const uint32_t *tile,
+                                          const uint32_t *scan, uint32_t dbase, uint32_t fbase, uint32_t cap, uint32_t pcap,
+                                          uint32_t nrec, PvFlowPacket *pk, PvFlowRecord *fr, uint32_t *next);
 // the DHCP handler's device stage (pv_dhcp.hip)
 extern "C" __global__ void pv_dhcp_scan(const uint8_t *recs, const uint32_t *offs, uint32_t n, uint32_t linktype, uint32_t ts_nano,
                                         const PvParams *P, unsigned long long *mask, uint32_t *cnt);
@@ -410,72 +419,7 @@ struct Window {
     uint32_t slot_at(uint64_t k) const { return (uint32_t)((ordinal + k) % PV_SLOTS); }
 };
 
-// ICON polynomial for lg_k = 11 (3rd/datasketches/cpc/include/icon_estimator.hpp:98-102)
-const double ICON11[20] = {
-    0.9999186020796150265, 0.3333249054574359826, 0.126791713589799987, -0.06662487271699729652,
-    -0.07335552427910230211, 0.3316370184815959909, -1.434143797561290068, 4.180260309967409604,
-    -8.593906870708760692, 12.95088874800289958, -14.56876092520539956, 12.37074367531410068,
-    -7.969152075707960137, 3.888774396648960074, -1.424923326506990051, 0.385084561785229984,
-    -0.07435541911616409816, 0.009695363567476529554, -0.0007644375960047160388, 2.75156194717188011e-05};
-
-inline double icon11(uint32_t c)
-{
-    if (c < 2) return c == 0 ? 0.0 : 1.0;
-    const double k = 2048.0, dc = (double)c;
-    if (dc > 5.7 * k) return 0.7940236163830469 * k * pow(2.0, dc / k);
-    const double x = dc / (2.0 * k);
-    double t = ICON11[19];
-    for (int j = 18; j >= 0; j--) t = t * x + ICON11[j];
-    const double r = dc / k;
-    const double res = dc * t * (1.0 + r * r * r / 66.774757);
-    return res >= dc ? res : dc;
-}
-
-// HIP estimate replayed from coupons in first-occurrence order, with the
-// sparse->windowed promotion and the kxp refresh of every 8th window move
-// (cpc_sketch_impl.hpp:196-380).
-inline double cpc_hip(std::vector<std::pair<int64_t, uint32_t>> &firsts)
-{
-    std::sort(firsts.begin(), firsts.end());
-    std::vector<uint64_t> rows(2048, 0);
-    static double kxp_byte[256];
-    static bool init = false;
-    if (!init) {
-        for (int b = 0; b < 256; b++) {
-            double s = 0;
-            for (int c = 0; c < 8; c++) if (!((b >> c) & 1)) s += ldexp(1.0, -(c + 1));
-            kxp_byte[b] = s;
-        }
-        init = true;
-    }
-    double kxp = 2048.0, hip = 0;
-    uint32_t C = 0;
-    int w = 0;
-    bool windowed = false;
-    for (auto &f : firsts) {
-        uint32_t row = f.second >> 6, col = f.second & 63;
-        rows[row] |= 1ull << col;
-        C++;
-        hip += 2048.0 / kxp;
-        kxp -= ldexp(1.0, -(int)(col + 1));
-        if (!windowed) {
-            if (((uint64_t)C << 5) >= 3ull * 2048) windowed = true;
-        } else if (((uint64_t)C << 3) >= (27ull + ((uint64_t)w << 3)) * 2048) {
-            w++;
-            if ((w & 7) == 0) {
-                double bs[8] = {0};
-                for (int i = 0; i < 2048; i++) {
-                    uint64_t word = rows[i];
-                    for (int j = 0; j < 8; j++) { bs[j] += kxp_byte[word & 0xff]; word >>= 8; }
-                }
-                double tot = 0;
-                for (int j = 7; j >= 0; j--) tot += ldexp(1.0, -8 * j) * bs[j];
-                kxp = tot;
-            }
-        }
-    }
-    return hip;
-}
+// (the CPC estimators icon11 / cpc_hip: pv_cpc.h)
 
 // libs/visor_dns/dns.h:31-265 name tables (IANA registry values, reference spellings)
 inline const std::map<uint16_t, const char *> &qtype_names()
@@ -1036,6 +980,25 @@ struct pv_ctx {
     std::vector<uint8_t> h_bg_arena;
     double bgp_scan_ms = 0; // stamped pv_bgp_scan launches (pv_set_kernel_timing)
     uint64_t bgp_scan_launches = 0;
+    // The flow handler (pv_set_flow; null = not attached), laid out as the DHCP handler's and kept at
+    // the end of the context, so that no field the other passes use moves: per-tile
+    // masks, the four per-tile count arrays laid end to end with their exclusive scan, a round's
+    // datagrams (flow_pcap) and flow records (flow_cap + PV_FLOW_SLACK), where the next round begins
+    std::unique_ptr<pvflow::Manager> flow;
+    PvFlowPorts flow_ports{};
+    uint32_t flow_cap = 0, flow_pcap = 0;
+    unsigned long long *d_fl_mask = nullptr;
+    uint32_t *d_fl_tile = nullptr, *d_fl_rank = nullptr, *d_fl_next = nullptr;
+    PvFlowPacket *d_fl_pk = nullptr;
+    PvFlowRecord *d_fl_fr = nullptr;
+    PvParams *d_fl_params = nullptr;
+    void *d_fl_scan = nullptr;
+    size_t fl_scan_bytes = 0;
+    std::vector<PvFlowPacket> h_fl_pk;
+    std::vector<PvFlowRecord> h_fl_fr;
+    double flow_scan_ms = 0; // stamped pv_flow_scan launches (pv_set_kernel_timing)
+    uint64_t flow_scan_launches = 0;
+    uint64_t flow_stats[3] = {0, 0, 0}; // datagrams accepted, payloads refused, of those version 9 / 10
 };
 
 // PV_HOST_PROF mark k: host time since the previous mark goes to hprof[k]

@@ -1378,6 +1378,15 @@ int pv_window_json(pv_ctx *c, uint32_t period, int merged, char **out)
         j.sep();
         j.s += pvbgp::Manager::json(b);
     }
+    if (c->flow) {
+        // and the flow handler's (pv_flow.cpp)
+        pvflow::Bucket b;
+        std::string err;
+        if (!c->flow->window(period, merged != 0, b, err)) return c->fail(PV_EINVAL, "%s", err.c_str());
+        j.key("flow");
+        j.sep();
+        j.s += c->flow->json(b, c->cfg.topn_count, c->cfg.topn_percentile_threshold);
+    }
     j.end_obj();
     *out = strdup(j.s.c_str());
     return 0;
@@ -1470,6 +1479,7 @@ int pv_bucket_merge(pv_ctx *c, uint32_t handler, pv_bucket **bucket, uint32_t pe
 {
     if (handler == PV_HANDLER_DHCP) return c->fail(PV_EUNSUPPORTED, "bucket merge: external buckets are not built for the DHCP handler");
     if (handler == PV_HANDLER_BGP) return c->fail(PV_EUNSUPPORTED, "bucket merge: external buckets are not built for the BGP handler");
+    if (handler == PV_HANDLER_FLOW) return c->fail(PV_EUNSUPPORTED, "bucket merge: external buckets are not built for the flow handler");
     if (!bucket || (handler != PV_HANDLER_NET && handler != PV_HANDLER_DNS)) return c->fail(PV_EINVAL, "bucket merge: one handler");
     std::lock_guard<std::mutex> g(c->mu); // values drained under the lock (pv_window_json)
     int rc = sync_xvals(c);
@@ -1597,6 +1607,7 @@ int pv_window_prometheus(pv_ctx *c, uint32_t period, uint32_t handlers, const ch
                          const char *const *label_values, uint32_t n_labels, char **out)
 {
     *out = nullptr;
+    if (handlers & PV_HANDLER_FLOW) return c->fail(PV_EUNSUPPORTED, "window_prometheus: not built for the flow handler");
     std::lock_guard<std::mutex> g(c->mu); // values drained under the lock (pv_window_json)
     int rc = sync_xvals(c);
     if (rc) return rc;
@@ -1654,6 +1665,7 @@ int pv_window_opentelemetry(pv_ctx *c, uint32_t period, uint32_t handlers, const
     *bytes = 0;
     if (handlers & PV_HANDLER_DHCP) return c->fail(PV_EUNSUPPORTED, "window_opentelemetry: not built for the DHCP handler");
     if (handlers & PV_HANDLER_BGP) return c->fail(PV_EUNSUPPORTED, "window_opentelemetry: not built for the BGP handler");
+    if (handlers & PV_HANDLER_FLOW) return c->fail(PV_EUNSUPPORTED, "window_opentelemetry: not built for the flow handler");
     std::lock_guard<std::mutex> g(c->mu); // values drained under the lock (pv_window_json)
     int rc = sync_xvals(c);
     if (rc) return rc;

@@ -161,6 +161,11 @@ def process_shard(handlers, recs, index, start_sec: int, start_nsec: int = 0, gr
         from pktvisor_amd import PvError
         raise PvError("process_shard failed (-4): the multi-GPU reduce does not carry BGP state "
                       "(a BGP handler is attached): process the capture on one rank")
+    if getattr(handlers, "flow_attached", False):
+        # nor the flow manager's buckets: devices, interfaces, coupons
+        from pktvisor_amd import PvError
+        raise PvError("process_shard failed (-4): the multi-GPU reduce does not carry flow state "
+                      "(a flow handler is attached): process the capture on one rank")
     handlers.set_start_tstamp(start_sec, start_nsec)
     if not getattr(handlers, "slow_defer", False):
         try:
